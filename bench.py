@@ -6,7 +6,12 @@ K rootless bcasts (random originators, 64-byte payloads by default) across the
 world's ranks until every rank has picked up every bcast it is owed.  Inputs
 (schedule, rings) are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds every other leg
+(latency, decisions, payload sizes, small worlds, bulk, mixed sizes, the drop-in API beside the reference,
+live PMC traffic, CPU baselines and the oracle check of the legs' results); the --no-* options trim a --full run.
+--dump-outputs DIR writes what the last timed step delivered (per-rank statistics) as DIR/<name>.npy.
 
 N = 1: one GPU hosts a 256-rank world (256 workgroup-ranks).
 N > 1 (torch.distributed.run, one process per GPU): ONE world of 256 x N ranks,
@@ -73,6 +78,29 @@ def dump_write(rank):
     os.makedirs(_DUMP["dir"], exist_ok=True)
     with open(os.path.join(_DUMP["dir"], "rank%d.json" % rank), "w") as f:
         json.dump(_DUMP["recs"], f)
+
+
+# --dump-outputs: the per-rank results of the timed storm's last step a caller reads back (World.stats()) that the
+# program alone determines (clocks and iteration counts are left out)
+_OUTPUT_FIELDS = ("bcast_delivered", "bcast_sum", "originated", "error", "unmarked_slots")
+
+
+def dump_outputs(d, st, world, rank):
+    """DIR/<name>.npy, float64, one value per rank of this part (N > 1: <name>.part<k>.npy).  bcast_sum is a 64-bit
+    checksum: written as its low and high 32-bit halves, each exact in float64"""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else ".part%d" % rank
+    for f in _OUTPUT_FIELDS:
+        a = np.asarray(st[f], dtype=np.uint64)
+        if f == "bcast_sum":
+            cols = {f + "_lo32": a & np.uint64(0xFFFFFFFF), f + "_hi32": a >> np.uint64(32)}
+        else:
+            assert int(a.max(initial=0)) < 1 << 53, f
+            cols = {f: a}
+        for name, v in cols.items():
+            np.save(os.path.join(d, name + sfx + ".npy"), v.astype(np.float64))
 
 
 def cpu_baseline(n, length, seed, target_s, bulk=None):
@@ -732,7 +760,16 @@ def main():
     ap.add_argument("--no-bulk", action="store_true", help="skip the large-message leg (vs RCCL at N > 1)")
     ap.add_argument("--dump", default="", help="directory: every rank writes its ranks' per-leg statistics there "
                                                 "(tests/test_gpu_multigpu.py checks them against the oracle)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the timed storm (latency, decisions, "
+                                                        "payload sizes, small worlds, bulk, mixed sizes, drop-in API, "
+                                                        "PMC traffic, CPU baselines); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the per-rank results of the last timed "
+                                                                      "step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the timed storm and its result line only
+        args.no_cpu_baseline = args.no_extras = args.no_pmc = args.no_api = args.no_bulk = True
     _DUMP["dir"] = args.dump
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -839,6 +876,8 @@ def main():
     elapsed = max_over_ranks(time.perf_counter() - t0)
     st = w.stats()
     dump_leg("storm", w, st, seed=seed, k=k, len=length, world_ranks=R)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, st, world, rank)
     ok &= bool((st["error"] == 0).all())
     copies = world if mode == "replicas" else 1  # independent worlds each run the whole storm
     ok &= int(sum_over_ranks(float(st["originated"].sum()))) == k * copies

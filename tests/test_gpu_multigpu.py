@@ -223,7 +223,7 @@ def _bench_parts(parts, per, port, limit, pool_cap=None):
     dump = tempfile.mkdtemp(prefix="rlo_dump")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(parts), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", str(parts), "--steps", "2",
-           "--warmup", "1", "--ranks", str(per), "--k", "16384", "--lat-rounds", "200", "--no-api", "--no-pmc",
+           "--warmup", "1", "--ranks", str(per), "--k", "16384", "--lat-rounds", "200", "--full", "--no-api", "--no-pmc",
            "--no-cpu-baseline", "--dump", dump]
     # Bounded below the suite's per-test limit, output to files (torchrun's workers outlive a killed
     # agent's pipes), so a stall fails with the bench's own progress lines instead of a bare timeout

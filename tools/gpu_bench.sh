@@ -1,10 +1,11 @@
-# the default bench line (python bench.py), stderr progress kept
+# the full bench line (python bench.py --full), stderr progress kept (under ${RLO_OUT_DIR:-bench_out}/${RLO_OUT:-r6}/)
 set -o pipefail
 tag=${1:-bench}
-mkdir -p gpurun_out/${RLO_OUT:-r6}
-timeout -k 10 900 python3 -u bench.py > gpurun_out/${RLO_OUT:-r6}/$tag.json 2> gpurun_out/${RLO_OUT:-r6}/$tag.err || { tail -20 gpurun_out/${RLO_OUT:-r6}/$tag.err; exit 1; }
-tail -3 gpurun_out/${RLO_OUT:-r6}/$tag.err
-python3 - gpurun_out/${RLO_OUT:-r6}/$tag.json <<'PY'
+d=${RLO_OUT_DIR:-bench_out}/${RLO_OUT:-r6}
+mkdir -p $d
+timeout -k 10 900 python3 -u bench.py --full > $d/$tag.json 2> $d/$tag.err || { tail -20 $d/$tag.err; exit 1; }
+tail -3 $d/$tag.err
+python3 - $d/$tag.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 keys = ["value", "ms_per_step", "p50_us", "p99_us", "decisions_per_s", "decisions_per_s_pend_hbm", "pend_hbm_cost",

@@ -11,5 +11,5 @@ cat $d/hop_ab_$tag.txt
 timeout -k 10 120 python3 -u tools/round_timeline.py --n 8 --sizes 64 --rounds 64 > $d/tl_hop_$tag.txt 2>&1 || exit $?
 RLO_NO_HOP=1 timeout -k 10 120 python3 -u tools/round_timeline.py --n 8 --sizes 64 --rounds 64 > $d/tl_full_$tag.txt 2>&1 || exit $?
 tail -25 $d/tl_hop_$tag.txt; tail -25 $d/tl_full_$tag.txt
-timeout -k 10 300 python3 -u bench.py > $d/bench_$tag.json 2> $d/bench_$tag.err || exit $?
+timeout -k 10 300 python3 -u bench.py --full > $d/bench_$tag.json 2> $d/bench_$tag.err || exit $?
 cat $d/bench_$tag.json

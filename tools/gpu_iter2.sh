@@ -11,7 +11,7 @@ cat $d/api_ab_$tag.txt
 timeout -k 10 120 python3 -u tools/round_timeline.py --n 8 --sizes 64 --rounds 64 > $d/tl_hop_$tag.txt 2>&1 || exit $?
 RLO_NO_HOP=1 timeout -k 10 120 python3 -u tools/round_timeline.py --n 8 --sizes 64 --rounds 64 > $d/tl_full_$tag.txt 2>&1 || exit $?
 tail -3 $d/tl_hop_$tag.txt; tail -3 $d/tl_full_$tag.txt
-timeout -k 10 300 python3 -u bench.py > $d/bench_$tag.json 2> $d/bench_$tag.err || exit $?
+timeout -k 10 300 python3 -u bench.py --full > $d/bench_$tag.json 2> $d/bench_$tag.err || exit $?
 python3 -c "
 import json,sys; b=json.load(open('$d/bench_$tag.json'))
 print('value', b['value'], 'p50', b['p50_us'], 'dec', b['decisions_per_s'], 'pool16', b['pool16_decisions_per_s'])
