@@ -17,6 +17,9 @@
  *   latency : one bcast at a time, completion latency per round
  *   iar     : every rank runs its own proposal list, device judge, vote AND,
  *             decision bcast (RLO_submit_proposal :876 ... _iar_decision_handler :814)
+ *   send    : rootless bcasts of caller-owned device buffers: payloads read from a source buffer in device
+ *             memory, every receiver's copy written to a destination buffer in device memory (the hop kernel only)
+ *   host    : the host-service program under the drop-in rootless_ops.h (commands and pickups in host memory)
  */
 #ifndef RLO_HIP_H
 #define RLO_HIP_H
@@ -134,7 +137,9 @@ int rlo_world_create(const rlo_world_cfg_t* cfg, rlo_world_t** out);
                                  * hop kernel on ONE XCD, so a hand-off store stays in that XCD's L2 and the
                                  * consumer's load hits it (one hop 0.51 vs 1.11 us, tools/xcd_probe.hip).  Only the
                                  * hop kernel's programs run (latency; iar with pool 1, <= 16 ranks, device judges);
-                                 * a launch that needs the progress kernel returns RLO_E_INVAL */
+                                 * a launch that needs the progress kernel returns RLO_E_INVAL.  The hop kernel holds
+                                 * a message in its wave's 64 lanes (the header + 63 16-B chunks), so its programs'
+                                 * messages are at most 1008 bytes: a longer latency round is refused here too */
 #define RLO_PART_CHUNKED 2u  /* bulk messages take the multi-GPU plan (chunked scatter + all-gather) even when every
                                  * part is on one GPU: the 8-GPU path, rehearsed on one (every part must set it alike) */
 typedef struct {
@@ -222,6 +227,41 @@ int rlo_program_latency(rlo_world_t* w, uint32_t rounds, uint32_t len, uint64_t 
  * a bulk announcement when its forwards were issued and when wave 0's next spin began (a ring-slot message the
  * doorbell pass took: two probes inside that pass), two probes inside the lone-message path.  Copies rows * *stride words to out (cap words), returns the rows copied. */
 int rlo_timeline(rlo_world_t* w, uint32_t* out, uint64_t cap, uint32_t* stride);
+
+/* send: rootless bcasts of CALLER-OWNED DEVICE BUFFERS.  Message i is a reference-style bcast (tag BCAST, header id
+ * i, origin origin[i]; rootless_ops.c:1581-1604) whose payload the originating rank-wave reads from `src` in device
+ * memory; every rank but the origin (:583-589) writes the payload it receives to its place in `dst`: bytes [0, len)
+ * are the source's, [len, round16(len)) zero (the message's last 16-B chunk as it travels), the rest of the place and
+ * the origin's own place for its own message are not written.  No byte crosses the host.  Same skip-ring tree, rings
+ * and doorbells as every program.  rlo_stats: bcast_delivered, originated, bcast_sum (the per-message checksum of
+ * the storm / latency programs), error.  RLO_FLAG_LOG: the delivery records (origin, tree parent, id, len) without
+ * payload copies -- dst is the payload.  RLO_SEND_ORDERED: rlo_latencies() as for the latency program.
+ * The hop kernel (rlo_hop.hip) alone runs it: a launch that cannot run that kernel (a bulk world, ranks not
+ * co-resident, a diagnostics mode that forces the progress kernel) returns RLO_E_INVAL before anything is reset, never
+ * the progress kernel.  Worlds of several parts (one process or several) are supported, each part passing its own
+ * src and dst.  RLO_PART_ONE_XCD worlds are refused here (RLO_E_INVAL): whether a ring line cached in the XCD's L2
+ * survives from one launch into a DIFFERENT program of the next is not settled, and this program's launches differ
+ * by design (other origins, lengths and buffers every time), so it does not ride on that.
+ * The launch ends by itself with RLO_DERR_TIMEOUT after 10 s without progress on a rank or 120 s in all. */
+#define RLO_SEND_ORDERED 0x100u  /* rlo_send_cfg_t.flags: one message in flight, message i+1 originates when every rank has
+                                    picked up message i (the latency program's closed loop): a TOTAL order.  Without it every
+                                    rank originates its own messages as fast as its out-rings take them (per-origin FIFO only) */
+typedef struct {
+    int64_t k;              /* messages, 1 .. 2^31-1 (ORDERED in a world of several parts: <= 8192, the latency program's limit) */
+    const int32_t* origin;  /* host [k]: the rank that originates message i (any rank, any mix)                     */
+    const uint32_t* len;    /* host [k]: bytes of message i, 1 .. slot; NULL = every message is `slot` bytes        */
+    const void* src;        /* DEVICE, 16-B aligned, k * slot bytes: message i's bytes at i * slot.  This part reads only
+                               the messages its own ranks originate.  Must not change while the launch runs      */
+    void* dst;              /* DEVICE, 16-B aligned, n_local * k * slot bytes: local rank lr's copy of message i at
+                               (lr * k + i) * slot                                                                 */
+    uint32_t slot;          /* bytes per message place: a multiple of 16, <= 1008 (63 chunks + the header = the hop
+                               kernel's 64 lanes) and <= the world's max_payload rounded up to 16                 */
+    uint32_t flags;         /* RLO_FLAG_LOG | RLO_FLAG_HIST | RLO_SEND_ORDERED                                      */
+    uint32_t log_cap, pad;
+} rlo_send_cfg_t;
+int rlo_program_send(rlo_world_t* w, const rlo_send_cfg_t* cfg);
+/* the argument checks of rlo_program_send that need no GPU (pure host): RLO_OK or RLO_E_INVAL */
+int rlo_send_check(const rlo_send_cfg_t* cfg, int n_ranks, uint32_t max_payload);
 
 #define RLO_JUDGE_APPROVE 0u /* approve everything                                           */
 #define RLO_JUDGE_MASK 1u    /* decline iff mask[rank] != 0 (arg != NULL)                     */

@@ -74,6 +74,7 @@ enum Mode : uint32_t {
     MODE_HOPPROF = 131072u,  // diagnostics build: shader clocks at points of a doorbell hop into stats.prof (tools/hop_prof.py)
     MODE_NOHPW = 262144u,   // diagnostics build, host mode A/B: no wave-1 host poller (wave 0 polls the host words itself)
     MODE_XCD1 = 524288u,    // RLO_PART_ONE_XCD: the hop kernel's rank-waves on one XCD, L2-kept (plain) hand-off stores
+    MODE_SEND = 1048576u,   // the send program (rlo_hop.hip, the SEND instantiations only): bcasts of caller-owned device buffers
     MODE_CORRUPT = 65536u,  // diagnostics build, test of the VERIFY check: a direct scatter zeroes one granule of one copy
     MODE_HOST = 128u,  // host-service: originations / judge verdicts come from a host command ring,
                        //   deliveries / judge requests / results go to a host pickup ring (rootless_ops.h)
@@ -301,6 +302,12 @@ struct Params {
     uint32_t storm_order;           // RLO_ORDER_SLOTS: bcast b originates at b mod N
     uint32_t host_judge;            // host mode: 1 = judges are the host's callbacks, 0 = the device registry
     uint32_t hop_chunks;            // the hop kernel (rlo_hop.hip): 16-B chunks of the program's longest message
+    // the send program (MODE_SEND; appended: the kernarg offsets above are those of every earlier build).  The own lists
+    // are lat_own_off / lat_own (the ids each local rank originates, ascending); send_own_len runs beside lat_own
+    const uint8_t* send_src;        // DEVICE, caller-owned: message i's bytes at i * send_slot
+    uint8_t* send_dst;              // DEVICE, caller-owned: local rank lr's copy of message i at (lr * send_k + i) * send_slot
+    const uint32_t* send_own_len;   // [lat_own entries] bytes of each own message
+    uint32_t send_k, send_slot;     // messages; bytes per message place (a multiple of 16, <= 1008)
 };
 
 // ---- bulk messages (longer than a ring slot; SURVEY §8(f)1, BASELINE configs[2], [4]).

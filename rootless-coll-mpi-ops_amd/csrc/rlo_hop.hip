@@ -1,4 +1,4 @@
-// rlo_hop.hip -- the hop kernel (gfx950 / CDNA4): the latency and iar programs on ONE wave per rank.
+// rlo_hop.hip -- the hop kernel (gfx950 / CDNA4): the latency, iar and send programs on ONE wave per rank.
 //
 // The programs that move one message at a time -- the latency program (one bcast in flight, rootless_ops.c
 // testcases.c:59-108 at scale) and the iar program (proposal / vote / decision rounds with device judges,
@@ -20,7 +20,8 @@
 //            forwarded into every child's ring and doorbell), then the delivery / proposal / decision effects
 //            (:583-615, :668-726, :814-859); a message whose out-rings are full waits (the ring stops there)
 //   own    : the pool's decisions (_iar_decision_bcast :908-917), then its next proposals (RLO_submit_proposal
-//            :876-906), or this rank's next latency round (RLO_bcast_gen :1581-1604)
+//            :876-906), or this rank's next latency round (RLO_bcast_gen :1581-1604), or (the send program) its next
+//            messages from the caller's source buffer
 //   publish: one drain of the round's stores, then its counters (vmcnt counts loads and stores in issue order)
 //
 // Rings, doorbells, counters, pending tables, logs and statistics are the world's own (rlo_world.cpp builds them
@@ -75,8 +76,17 @@ enum HopCnt : int {
 // RLO_PART_ONE_XCD): the grid is 8 workgroups per rank and only every eighth runs a rank (workgroups 8 apart share an
 // XCD; checked at launch), the rings are in cached memory and the hand-off stores are plain, so a line stays in that
 // XCD's L2 and the consumer's sc1 load hits it (tools/xcd_probe.hip: one hop 0.51 us vs 1.11 us)
-template <bool PH, bool SYS, bool LOC>
+//
+// SEND (MODE_SEND, rlo_program_send): the send program -- bcasts whose payload an originating rank-wave reads from the
+// caller's source buffer in device memory and every receiver writes to its place in the caller's destination buffer
+// (DESIGN.md 4.0.3).  Open loop (every rank originates its own messages as its out-rings take them) or, with MODE_LAT
+// set beside it, the latency program's closed loop (RLO_SEND_ORDERED).  No pending table, no one-XCD form: instantiated
+// for <false, false, false, true> and <false, true, false, true> only; every statement of it sits under
+// `if constexpr (SEND)`, so the other instantiations are what they were
+constexpr uint32_t kSendBurst = 4;  // open loop: originations per round at most, so taking ring messages is never starved
+template <bool PH, bool SYS, bool LOC, bool SEND = false>
 __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
+    static_assert(!SEND || (!PH && !LOC), "the send program has no pending table and no one-XCD form");
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
     __shared__ HopShared S;
     if constexpr (LOC)
@@ -110,7 +120,7 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
     __syncthreads();
     const uint64_t t_start = now_ticks();
     unsigned long long acc_sum = 0;  // checksum of delivered bcast chunks (this lane's share)
-    const int64_t expect_bcast = lat ? P.expect_bcast[lr] : 0;
+    const int64_t expect_bcast = (lat || SEND) ? P.expect_bcast[lr] : 0;
     const int64_t expect_dec = iar ? P.expect_dec[lr] : 0;
     const uint32_t my_mask = (iar && P.judge_kind == JUDGE_MASK) ? P.judge_mask[me] : 0u;
 
@@ -188,6 +198,35 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
     const uint32_t lat_pos_n = lat ? P.lat_own_off[lr + 1] - P.lat_own_off[lr] : 0u;
     uint32_t lat_own_next = lat_pos_n ? P.lat_own[P.lat_own_off[lr]] : 0xffffffffu;
     if (iar) prefetch_meta(0);
+    // the send program: my own messages (lat_pos counts them).  Lane j holds the id and the length of own message
+    // win_base + j -- one vector load each per 64 messages, issued at the end of a round and landed by the next poll's
+    // wait; sx_v is this lane's chunk of own message sx_pos (lane q = chunk q >= 1, from src + id * slot + 16 (q - 1)
+    // through a resource over that message's place alone: k * slot bytes can exceed the 4 GiB one resource spans),
+    // loaded when the message before it went out and left in flight while the round runs (vector loads, for the reason
+    // given at nx_i above)
+    uint32_t snd_off = 0, snd_n = 0, win_base = 0, win_id = 0, win_len = 0, sx_pos = 0xffffffffu;
+    u32x4 sx_v = {0u, 0u, 0u, 0u};
+    auto send_window = [&](uint32_t base) {
+        win_base = base;
+        const uint32_t cnt = min(snd_n - base, 64u);
+        const uint32_t off = (uint32_t)lane < cnt ? 4u * (uint32_t)lane : kOob;
+        win_id = __builtin_amdgcn_raw_buffer_load_b32(mk_rsrc(const_cast<uint32_t*>(P.lat_own) + snd_off + base, 4u * cnt), off, 0, 0);
+        win_len = __builtin_amdgcn_raw_buffer_load_b32(mk_rsrc(const_cast<uint32_t*>(P.send_own_len) + snd_off + base, 4u * cnt), off, 0, 0);
+    };
+    auto send_fetch = [&](uint32_t pos) {  // (pos inside the window)
+        const uint32_t id = rdl32(win_id, (int)(pos - win_base));
+        const __amdgpu_buffer_rsrc_t rs = mk_rsrc(const_cast<uint8_t*>(P.send_src) + (uint64_t)id * P.send_slot, P.send_slot);
+        sx_v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane >= 1 ? 16u * ((uint32_t)lane - 1u) : kOob, 0, 0);
+        sx_pos = pos;
+    };
+    if constexpr (SEND) {
+        snd_off = P.lat_own_off[lr];
+        snd_n = P.lat_own_off[lr + 1] - snd_off;
+        if (snd_n) {
+            send_window(0);
+            send_fetch(0);
+        }
+    }
     // MODE_TL (diagnostics build): this round's poll issued / returned, counters published, ring loop entered
     uint32_t tl_iss = 0, tl_back = 0, tl_pub = 0, tl_loop = 0;
     uint64_t idle_since = 0;
@@ -337,6 +376,11 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
             err(ERR_BAD_SLOT, w0);
             return true;
         }
+        if constexpr (SEND)  // a message with no place in dst (and: this program has no pending table for the other tags)
+            if (tag != TAG_BCAST || id >= P.send_k || len > P.send_slot) {
+                err(ERR_BAD_SLOT, w0);
+                return true;
+            }
         int judge = 1;
         u32x4 pe = {0u, 0u, 0u, 0u};
         if (tag != TAG_BCAST) pe = pend_rd(origin, pseq);
@@ -388,6 +432,13 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
                 if (P.mode & MODE_LOG) li = log_put<kPmHop>(S, P, lr, LOG_DELIVER | (TAG_BCAST << 8), origin, from, id, len, -1, tn - t0);
             }
             if (q < nch) acc_sum += q == 0 ? chunk_mix(0xFFFFFFFFu, u32x4{(uint32_t)origin, id, TAG_BCAST, len}) : chunk_mix(q - 1u, v);
+            if constexpr (SEND) {
+                // the payload chunks to this rank's place for message id (id < send_k, len <= send_slot: checked above).
+                // The resource covers that place alone, so the hardware drops whatever would fall outside it.  Ordinary
+                // stores, no hand-off: nothing in the launch reads dst
+                const __amdgpu_buffer_rsrc_t rd = mk_rsrc(P.send_dst + ((uint64_t)(uint32_t)lr * P.send_k + id) * P.send_slot, P.send_slot);
+                if (q >= 1u && q < nch) __builtin_amdgcn_raw_buffer_store_b128(v, rd, 16u * (q - 1u), 0, 0);
+            }
             if (P.mode & MODE_LOG) {
                 li = rdl32(li, 0);
                 if (li != ~0u && q >= 1u && q < nch && 16u * q <= P.log_stride)
@@ -787,7 +838,42 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
                 progressed = true;
             }
         }
-        if (lat && lat_own_next != 0xffffffffu && latr == lat_own_next) {
+        if constexpr (SEND) {
+            // the send program: my next own messages (RLO_bcast_gen :1581-1604 with the caller's bytes).  Open loop: while
+            // the out-rings take them, kSendBurst a round at most; ordered (lat): the one whose id the round word shows.  A
+            // refused origination waits for room and the round goes on (never a spin in here: ring messages are taken
+            // while originations wait, DESIGN.md 4 "Deadlock freedom")
+            for (uint32_t b = 0; b < kSendBurst && lat_pos < snd_n; b++) {
+                if (lat_pos - win_base >= 64u) {  // past the window: the next 64 ids and lengths, in by the next round
+                    send_window(lat_pos);
+                    progressed = true;
+                    break;
+                }
+                const uint32_t id = rdl32(win_id, (int)(lat_pos - win_base)), len = rdl32(win_len, (int)(lat_pos - win_base));
+                if (lat) {
+                    lat_own_next = id;
+                    if ((uint32_t)uni((int)latr) != id) break;
+                }
+                if (sx_pos != lat_pos) send_fetch(lat_pos);  // (not prefetched: fetch it now, one wait)
+                u32x4 v = sx_v;
+                {  // the zero-padded tail of the last chunk
+                    const int b0 = (int)len - (int)(16u * ((uint32_t)lane - 1u));
+                    v = u32x4{mask_bytes(v.x, b0), mask_bytes(v.y, b0 - 4), mask_bytes(v.z, b0 - 8), mask_bytes(v.w, b0 - 12)};
+                }
+                if (!originate((uint32_t)me | (TAG_BCAST << 16) | (0xffu << 24), id, len, v, out_head_r)) {
+                    room_wait = true;
+                    break;
+                }
+                HP_CNT(6, 1);
+                CNT_ADD(HC_ORIG, 1);
+                lat_pos++;
+                progressed = true;
+                if (lat) lat_own_next = 0xffffffffu;  // (the next round sets it from the window)
+                // the next one's chunks, in flight until it goes out
+                if (lat_pos < snd_n && lat_pos - win_base < 64u) send_fetch(lat_pos);
+                if (lat) break;
+            }
+        } else if (lat && lat_own_next != 0xffffffffu && latr == lat_own_next) {
             u32x4 v = {0u, 0u, 0u, 0u};
             if (lane >= 1 && (uint32_t)lane < ((kHdr + P.len + 15u) >> 4))
                 v = gen_chunk(P, K_LAT, me, lat_own_next, P.len, 0u, -1, (uint32_t)lane);
@@ -828,6 +914,7 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
         if ((n_iter & 1023u) == 0 && now_ticks() - t_start > P.deadline_ticks) err(ERR_TIMEOUT, 1);
         bool d = true;
         if (lat) d &= lat_pos >= lat_pos_n && (int64_t)rdl64(cnt_r, HC_BCAST) == expect_bcast;
+        if constexpr (SEND) d &= lat_pos >= snd_n && (int64_t)rdl64(cnt_r, HC_BCAST) == expect_bcast;
         if (iar)
             d &= own_iter == own_n && __ballot((uint32_t)lane < P.pend_slots && own_state_r != 0u) == 0ull &&
                  (int64_t)rdl64(cnt_r, HC_DEC) == expect_dec;
@@ -881,33 +968,37 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
 
 // C-ABI launch shims (rlo_world.cpp): one 64-thread workgroup per local rank, the pending table in dynamic LDS
 // (dyn_lds bytes) or, with Params.pend_hbm, in HBM (the PH instantiation); system-scope worlds run the SYS one
-template <bool PH, bool SYS, bool LOC = false>
+template <bool PH, bool SYS, bool LOC = false, bool SEND = false>
 static hipError_t hop_grant(size_t dyn_lds) {
     static size_t granted = 0;
     if (dyn_lds > granted) {
-        hipError_t e = hipFuncSetAttribute((const void*)rlo::rlo_hop_kernel<PH, SYS, LOC>,
+        hipError_t e = hipFuncSetAttribute((const void*)rlo::rlo_hop_kernel<PH, SYS, LOC, SEND>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
         if (e != hipSuccess) return e;
         granted = dyn_lds;
     }
     return hipSuccess;
 }
-template <bool PH, bool SYS, bool LOC = false>
+template <bool PH, bool SYS, bool LOC = false, bool SEND = false>
 static hipError_t hop_launch(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream) {
-    hipError_t e = hop_grant<PH, SYS, LOC>(dyn_lds);
+    hipError_t e = hop_grant<PH, SYS, LOC, SEND>(dyn_lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((rlo::rlo_hop_kernel<PH, SYS, LOC>), dim3(LOC ? 8 * blocks : blocks), dim3(64), dyn_lds, stream, *p);
+    hipLaunchKernelGGL((rlo::rlo_hop_kernel<PH, SYS, LOC, SEND>), dim3(LOC ? 8 * blocks : blocks), dim3(64), dyn_lds, stream, *p);
     return hipGetLastError();
 }
-template <bool PH, bool SYS>
+template <bool PH, bool SYS, bool SEND = false>
 static hipError_t hop_occ(int* blocks, size_t dyn_lds) {
-    hipError_t e = hop_grant<PH, SYS>(dyn_lds);
+    hipError_t e = hop_grant<PH, SYS, false, SEND>(dyn_lds);
     if (e != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, rlo::rlo_hop_kernel<PH, SYS, false>, 64, dyn_lds);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, rlo::rlo_hop_kernel<PH, SYS, false, SEND>, 64, dyn_lds);
 }
 
 extern "C" hipError_t rlo_launch_hop(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream) {
     const bool ph = p->pend_hbm != nullptr, sys = p->sys_scope != 0;
+    if (p->mode & rlo::MODE_SEND) {  // the send program: no one-XCD form, no pending table (its launch takes no dynamic LDS)
+        if ((p->mode & rlo::MODE_XCD1) || dyn_lds != 0 || !p->send_src || !p->send_dst) return hipErrorInvalidValue;
+        return sys ? hop_launch<false, true, false, true>(p, blocks, 0, stream) : hop_launch<false, false, false, true>(p, blocks, 0, stream);
+    }
     if ((p->mode & rlo::MODE_XCD1) && (sys || !p->xcd_word)) return hipErrorInvalidValue;  // (the rendezvous word)
     if (p->mode & rlo::MODE_XCD1)  // RLO_PART_ONE_XCD
         return ph ? hop_launch<true, false, true>(p, blocks, dyn_lds, stream) : hop_launch<false, false, true>(p, blocks, dyn_lds, stream);
@@ -921,6 +1012,17 @@ extern "C" hipError_t rlo_occupancy_hop(int* blocks, size_t dyn_lds, int ph) {
     hipError_t e = ph ? hop_occ<true, false>(&a, dyn_lds) : hop_occ<false, false>(&a, dyn_lds);
     if (e != hipSuccess) return e;
     e = ph ? hop_occ<true, true>(&b, dyn_lds) : hop_occ<false, true>(&b, dyn_lds);
+    if (e != hipSuccess) return e;
+    *blocks = a < b ? a : b;
+    return hipSuccess;
+}
+
+// the same for the send program's two instantiations
+extern "C" hipError_t rlo_occupancy_hop_send(int* blocks) {
+    int a = 0, b = 0;
+    hipError_t e = hop_occ<false, false, true>(&a, 0);
+    if (e != hipSuccess) return e;
+    e = hop_occ<false, true, true>(&b, 0);
     if (e != hipSuccess) return e;
     *blocks = a < b ? a : b;
     return hipSuccess;

@@ -33,6 +33,7 @@ extern "C" hipError_t rlo_occupancy(int* blocks, size_t dyn_lds, int variant);
 extern "C" hipError_t rlo_occupancy_ll(int* blocks, size_t dyn_lds, int variant);
 extern "C" hipError_t rlo_launch_hop(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream);
 extern "C" hipError_t rlo_occupancy_hop(int* blocks, size_t dyn_lds, int ph);
+extern "C" hipError_t rlo_occupancy_hop_send(int* blocks);
 
 static_assert(sizeof(rlo_rank_stats_t) == sizeof(rlo::RankStats), "stats ABI");
 static_assert(sizeof(rlo_log_rec_t) == sizeof(rlo::LogRec), "log ABI");
@@ -381,7 +382,7 @@ struct rlo_world {
     rlo::Params P{};
     DevBuf<int64_t> d_sched_off, d_expect_bcast, d_prop_off, d_expect_dec;
     DevBuf<uint32_t> d_sched_ids, d_prop_data_off, d_prop_data_len, d_isp_off, d_lat_count, d_lat_round;
-    DevBuf<uint32_t> d_lat_own_off, d_lat_own;
+    DevBuf<uint32_t> d_lat_own_off, d_lat_own, d_send_own_len;
     DevBuf<int32_t> d_lat_origin, d_prop_pid;
     DevBuf<uint64_t> d_lat_out, d_lat_obs;
     uint32_t* d_xcd = nullptr;  // RLO_PART_ONE_XCD: the placement check word (uncached)
@@ -1295,7 +1296,7 @@ int rlo_world_destroy(rlo_world_t* w) {
     w->d_sched_off.release(); w->d_expect_bcast.release(); w->d_prop_off.release(); w->d_expect_dec.release();
     w->d_sched_ids.release(); w->d_prop_data_off.release(); w->d_prop_data_len.release(); w->d_isp_off.release();
     w->d_lat_count.release(); w->d_lat_round.release(); w->d_lat_origin.release(); w->d_prop_pid.release();
-    w->d_lat_out.release(); w->d_lat_own_off.release(); w->d_lat_own.release(); w->d_mask.release(); w->d_prop_data.release(); w->d_log_payload.release();
+    w->d_lat_out.release(); w->d_lat_own_off.release(); w->d_lat_own.release(); w->d_send_own_len.release(); w->d_mask.release(); w->d_prop_data.release(); w->d_log_payload.release();
     w->d_isp.release(); w->d_log.release();
     if (w->d_xcd) (void)hipFree(w->d_xcd);
     host_free(w);
@@ -1530,6 +1531,86 @@ int rlo_program_latency(rlo_world_t* w, uint32_t rounds, uint32_t len, uint64_t 
         P.mode |= rlo::MODE_TL;
     }
     int rc = setup_log(w, flags, 0, true);
+    if (rc) return rc;
+    w->have_program = true;
+    return RLO_OK;
+}
+
+// the send program (rlo_hip.h rlo_send_cfg_t): what can be refused without a GPU
+int rlo_send_check(const rlo_send_cfg_t* cfg, int n_ranks, uint32_t max_payload) {
+    if (!cfg || n_ranks < 1 || cfg->k < 1 || cfg->k > 0x7FFFFFFFll || !cfg->origin) return RLO_E_INVAL;
+    const uint32_t slot = cfg->slot;
+    if (slot == 0 || (slot & 15u) || slot > 1008u || slot > (((uint64_t)max_payload + 15u) & ~15ull)) return RLO_E_INVAL;
+    if (!cfg->src || !cfg->dst || ((uintptr_t)cfg->src & 15u) || ((uintptr_t)cfg->dst & 15u)) return RLO_E_INVAL;
+    if (cfg->flags & ~(RLO_FLAG_LOG | RLO_FLAG_HIST | RLO_SEND_ORDERED)) return RLO_E_INVAL;
+    for (int64_t i = 0; i < cfg->k; i++) {
+        if (cfg->origin[i] < 0 || cfg->origin[i] >= n_ranks) return RLO_E_INVAL;
+        if (cfg->len && (cfg->len[i] == 0 || cfg->len[i] > slot)) return RLO_E_INVAL;
+    }
+    return RLO_OK;
+}
+
+int rlo_program_send(rlo_world_t* w, const rlo_send_cfg_t* cfg) {
+    if (!w || !cfg) return RLO_E_INVAL;
+    int rc = rlo_send_check(cfg, w->L.n, w->max_payload);
+    if (rc) return rc;
+    if (w->d_xcd) return RLO_E_INVAL;  // RLO_PART_ONE_XCD: refused (rlo_hip.h)
+    const bool ordered = (cfg->flags & RLO_SEND_ORDERED) != 0;
+    // ordered, sharded: the round word and counts are part 0's copy (rlo_device.hpp kLatWords)
+    if (ordered && w->L.nparts != 1 && cfg->k > rlo::kLatCap) return RLO_E_INVAL;
+    if (!w->connected) return RLO_E_NOTCONNECTED;
+    base_params(w);
+    rlo::Params& P = w->P;
+    const int nl = w->nl, rb = w->rb;
+    const uint32_t k = (uint32_t)cfg->k;
+    // per local rank the messages it originates, in order, and their lengths (the kernel loads 64 at a time)
+    std::vector<uint32_t> own_off(nl + 1, 0);
+    for (uint32_t i = 0; i < k; i++)
+        if (cfg->origin[i] >= rb && cfg->origin[i] < rb + nl) own_off[cfg->origin[i] - rb + 1]++;
+    std::vector<int64_t> expect(nl, 0);
+    for (int lr = 0; lr < nl; lr++) {
+        expect[lr] = (int64_t)k - own_off[lr + 1];
+        own_off[lr + 1] += own_off[lr];
+    }
+    std::vector<uint32_t> own(std::max<uint32_t>(own_off[nl], 1), 0), own_len(own.size(), 0), fill(own_off.begin(), own_off.end() - 1);
+    for (uint32_t i = 0; i < k; i++)
+        if (cfg->origin[i] >= rb && cfg->origin[i] < rb + nl) {
+            const uint32_t at = fill[cfg->origin[i] - rb]++;
+            own[at] = i;
+            own_len[at] = cfg->len ? cfg->len[i] : cfg->slot;
+        }
+    if (w->d_lat_own_off.upload(own_off) || w->d_lat_own.upload(own) || w->d_send_own_len.upload(own_len) ||
+        w->d_expect_bcast.upload(expect))
+        return RLO_E_HIP;
+    // (MODE_LL: the hop kernel always rings the doorbells, and only that kernel runs this program)
+    P.mode = rlo::MODE_SEND | rlo::MODE_LL | (ordered ? rlo::MODE_LAT : 0u) | ((cfg->flags & RLO_FLAG_HIST) ? rlo::MODE_HIST : 0u);
+    P.len = cfg->slot;
+    P.hop_chunks = 1u + cfg->slot / 16u;
+    P.lat_own_off = w->d_lat_own_off.p;
+    P.lat_own = w->d_lat_own.p;
+    P.send_own_len = w->d_send_own_len.p;
+    P.expect_bcast = w->d_expect_bcast.p;
+    P.send_src = static_cast<const uint8_t*>(cfg->src);
+    P.send_dst = static_cast<uint8_t*>(cfg->dst);
+    P.send_k = k;
+    P.send_slot = cfg->slot;
+    w->lat_rounds = 0;
+    w->tl_rows = 0;
+    if (ordered) {  // the latency program's closed loop: round word, delivery counts, completion ticks
+        if (w->d_lat_count.alloc(k) || w->d_lat_out.alloc(k) || w->d_lat_round.alloc(1) || w->d_lat_obs.alloc(k)) return RLO_E_HIP;
+        P.lat_rounds = k;
+        P.lat_count = w->d_lat_count.p;
+        P.lat_out = w->d_lat_out.p;
+        P.lat_round = w->d_lat_round.p;
+        P.lat_obs = w->d_lat_obs.p;
+        if (w->L.nparts != 1) {
+            uint64_t* blk = w->pc[0] + w->L.lat_base[0];
+            P.lat_round = reinterpret_cast<uint32_t*>(blk);
+            P.lat_count = reinterpret_cast<uint32_t*>(blk + 16);
+        }
+        w->lat_rounds = k;
+    }
+    rc = setup_log(w, cfg->flags, cfg->log_cap, false);  // records only: dst is the payload
     if (rc) return rc;
     w->have_program = true;
     return RLO_OK;
@@ -1977,8 +2058,10 @@ static size_t hop_lds(const rlo_world* w) {
 }
 static bool hop_eligible(rlo_world* w) {
     const rlo::Params& P = w->P;
-    if (!(P.mode & rlo::MODE_LL) || !(P.mode & (rlo::MODE_LAT | rlo::MODE_IAR))) return false;
+    const bool send = (P.mode & rlo::MODE_SEND) != 0;  // the send program: this kernel or none (rlo_launch_ex)
+    if (!(P.mode & rlo::MODE_LL) || !(P.mode & (rlo::MODE_LAT | rlo::MODE_IAR | rlo::MODE_SEND))) return false;
     if (P.mode & (rlo::MODE_HOST | rlo::MODE_STORM | rlo::MODE_PROF | rlo::MODE_HOPPROF | rlo::MODE_NOFAST)) return false;
+    if (send && ((P.mode & rlo::MODE_IAR) || w->d_xcd)) return false;
     // the timeline (diagnostics build) is the hop kernel's too unless RLO_TL_FULL asks for the progress kernel's
     static const bool tl_full = diag_env("RLO_TL_FULL") != nullptr;
     if ((P.mode & rlo::MODE_TL) && tl_full) return false;
@@ -1993,7 +2076,10 @@ static bool hop_eligible(rlo_world* w) {
     const size_t lds = hop_lds(w);
     if (lds > 64u * 1024u) return false;
     int b = 0;
-    if (rlo_occupancy_hop(&b, lds, P.pend_hbm ? 1 : 0) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if ((send ? rlo_occupancy_hop_send(&b) : rlo_occupancy_hop(&b, lds, P.pend_hbm ? 1 : 0)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
     // (RLO_PART_ONE_XCD: every rank-wave on the CUs of one XCD, an eighth of the GPU's)
     return b > 0 && (int64_t)b * (w->d_xcd ? w->cus / 8 : w->cus) >= (int64_t)w->nl;
 }
@@ -2004,6 +2090,9 @@ int rlo_launch_ex(rlo_world_t* w, void* stream, uint32_t flags) {
     if (!w->have_program) return RLO_E_NOPROGRAM;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(w->device));
+    // the send program runs the hop kernel or nothing, and that is settled before anything is reset or recorded (the
+    // diagnostics switches below that force the progress kernel included)
+    if ((w->P.mode & rlo::MODE_SEND) && (diag_env("RLO_NO_FAST") || diag_env("RLO_HOP_PROF") || !hop_eligible(w))) return RLO_E_INVAL;
     if (!(flags & RLO_LAUNCH_NO_RESET)) {
         int rc = rlo_reset(w, stream);
         if (rc) return rc;

@@ -33,8 +33,9 @@ RLO_LAUNCH_NO_RESET = 1
 RLO_TRIM_IMPORTS, RLO_TRIM_FREE, RLO_TRIM_RETIRED, RLO_TRIM_EXPORTED = 1, 2, 4, 8  # rlo_pool_trim
 RLO_FLAG_LOG, RLO_FLAG_HIST, RLO_FLAG_PROF, RLO_FLAG_TIMELINE = 1, 2, 4, 8
 RLO_JUDGE_APPROVE, RLO_JUDGE_MASK, RLO_JUDGE_ISP, RLO_JUDGE_HASH = 0, 1, 2, 3
+RLO_SEND_ORDERED = 0x100  # rlo_send_cfg_t.flags
 DERR = {1: "timeout", 2: "vote ring", 3: "pid collision", 4: "vote orphan", 5: "log full", 6: "bad slot", 7: "host command",
-        8: "bulk index"}
+        8: "bulk index", 9: "xcd placement"}
 # host-service program (rlo_hip.h)
 RLO_CMD_BCAST, RLO_CMD_PROPOSAL, RLO_CMD_JUDGE, RLO_CMD_OWN_JUDGE, RLO_CMD_QUIT = 0, 2, 16, 17, 18
 RLO_CMD_BULK, RLO_CMD_BULK_RELEASE = 10, 19
@@ -91,6 +92,12 @@ class IarCfg(ctypes.Structure):
                 ("log_cap", ctypes.c_uint32), ("pool", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+class SendCfg(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int64), ("origin", ctypes.c_void_p), ("len", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("dst", ctypes.c_void_p), ("slot", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("log_cap", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
 class HostCfg(ctypes.Structure):
     _fields_ = [("cmd_slots", ctypes.c_uint32), ("pickup_slots", ctypes.c_uint32), ("idle_timeout_s", ctypes.c_uint32),
                 ("flags", ctypes.c_uint32), ("pool", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
@@ -124,7 +131,7 @@ class LogRec(ctypes.Structure):
 EXPORTS = ["rlo_topology", "rlo_children", "rlo_world_create", "rlo_world_destroy", "rlo_part_close_imports", "rlo_part_import", "rlo_world_query",
            "rlo_part_create", "rlo_part_export", "rlo_part_connect", "rlo_reset", "rlo_launch_ex",
            "rlo_stream_create", "rlo_stream_destroy",
-           "rlo_program_storm", "rlo_program_latency", "rlo_program_iar", "rlo_launch", "rlo_wait", "rlo_run",
+           "rlo_program_storm", "rlo_program_latency", "rlo_program_iar", "rlo_program_send", "rlo_send_check", "rlo_launch", "rlo_wait", "rlo_run",
            "rlo_last_kernel_ms", "rlo_stats", "rlo_log", "rlo_latencies", "rlo_round_ticks", "rlo_timeline", "rlo_strerror", "rlo_last_hip_error",
            "rlo_device_error", "rlo_bulk_debug",
            "rlo_program_host", "rlo_host_post", "rlo_host_poll", "rlo_host_running", "rlo_host_cmd_count",
@@ -158,6 +165,8 @@ def load():
     L.rlo_program_storm.argtypes = [vp, ctypes.POINTER(StormCfg)]
     L.rlo_program_latency.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32]
     L.rlo_program_iar.argtypes = [vp, ctypes.POINTER(IarCfg), ctypes.c_int64, vp, vp, vp, vp, vp]
+    L.rlo_program_send.argtypes = [vp, ctypes.POINTER(SendCfg)]
+    L.rlo_send_check.argtypes = [ctypes.POINTER(SendCfg), ctypes.c_int, ctypes.c_uint32]
     L.rlo_part_create.argtypes = [ctypes.POINTER(PartCfg), ctypes.POINTER(vp)]
     L.rlo_part_export.argtypes = [vp, vp, ctypes.c_uint32]
     L.rlo_part_connect.argtypes = [vp, vp, ctypes.c_int]

@@ -8,7 +8,10 @@ run_processes(): one spawned process per part; blobs are exchanged through a que
 A program spec is a dict: {"kind": "storm", "k", "len", "seed", "window", "log", "len_max", "order"} or
 {"kind": "iar", "props": [(origin, pid, bytes)], "judge", "mask", "isp", "seed", "ppm", "log", "pool"} or
 {"kind": "lat", "rounds", "len", "seed"} (the round word lives in part 0; st["round_ticks"] is world
-rank 0's clock at each round's completion).
+rank 0's clock at each round's completion) or
+{"kind": "send", "origins", "slot", "src": the k * slot source bytes (NumPy), "lens", "ordered", "log", "fill"}: each
+part creates its own device buffers (dst pre-filled with `fill`, 0xA5), and st["dst"] is the world's destination
+bytes as a NumPy array [rank][message][slot].
 """
 import ctypes
 import multiprocessing as mp
@@ -33,15 +36,32 @@ def _program(w, spec):
                       log=spec.get("log", False), log_cap=spec.get("log_cap", 0), pool=spec.get("pool", 1))
     elif spec["kind"] == "lat":
         w.program_latency(spec["rounds"], spec["len"], seed=spec.get("seed", 0x5EED))
+    elif spec["kind"] == "send":
+        # the part's own device buffers: the whole source (a part reads only its own ranks' messages) and its ranks'
+        # destination places, pre-filled; both are in place before the launch (which runs on a stream of its own)
+        import torch
+
+        dev = torch.device("cuda", w.device if w.device >= 0 else torch.cuda.current_device())
+        k, slot = len(spec["origins"]), spec["slot"]
+        src = torch.from_numpy(np.ascontiguousarray(spec["src"], dtype=np.uint8).reshape(-1)).to(dev)
+        dst = torch.full((w.n_local * k * slot,), spec.get("fill", 0xA5), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        w._send_bufs = (src, dst)
+        w.program_send(spec["origins"], src, dst, slot, lens=spec.get("lens"), ordered=spec.get("ordered", False),
+                       log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False))
     else:
         raise ValueError(spec["kind"])
 
 
 def _collect(w, spec):
     st = w.stats()
+    if spec["kind"] == "send":
+        w.info_now()  # (last_kernel: the kernel this launch ran)
     out = {"rank_begin": w.rank_begin, "stats": st, "ms": w.kernel_ms(), "info": dict(w.info)}
     if spec["kind"] == "lat" and w.rank_begin == 0:
         out["rounds"] = w.round_ticks()
+    if spec["kind"] == "send":  # this part's destination buffer: [local rank][message][slot] bytes
+        out["dst"] = w._send_bufs[1].cpu().numpy().reshape(w.n_local, len(spec["origins"]), spec["slot"])
     if spec.get("log"):
         cap = spec.get("log_cap", 0) or 1024
         out["logs"] = {r: w.log(r, cap=cap, payload=spec["kind"] == "storm") for r in range(w.rank_begin, w.rank_end)}
@@ -57,6 +77,9 @@ def merge(results):
     # per world rank: its part's rlo_world_info_t.peers / sys_scope (where that part's peers are)
     for key in ("peers", "sys_scope"):
         st["part_" + key] = np.concatenate([np.full(len(r["stats"]["error"]), r["info"][key]) for r in results])
+    if "dst" in results[0]:  # the send program: every part's destination buffer, by world rank, and the kernel it ran
+        st["dst"] = np.concatenate([r["dst"] for r in results])
+        st["part_last_kernel"] = np.concatenate([np.full(len(r["stats"]["error"]), r["info"]["last_kernel"]) for r in results])
     logs = {}
     for r in results:
         logs.update(r.get("logs", {}))

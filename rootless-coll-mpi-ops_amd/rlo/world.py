@@ -8,6 +8,8 @@ Programs map the reference's application loops onto the device:
                 (rootless_ops.c:311, :1581, :538, :938; testcases.c:638-697)
   latency()  -- one bcast at a time (test_gen_bcast style, testcases.c:59-108)
   iar()      -- RLO_submit_proposal / vote / decision (rootless_ops.c:668-917)
+  send()     -- bcasts of the caller's own device buffers, device memory to device memory (program_send,
+                bcast_tensor; the hop kernel only)
 """
 import ctypes
 
@@ -48,6 +50,7 @@ class World:
             check(self.lib.rlo_part_create(ctypes.byref(cfg), ctypes.byref(h)), "rlo_part_create")
         self.h = h
         self.n = n
+        self.device = device
         self._query()
         self._lat_rounds = 0
 
@@ -178,6 +181,72 @@ class World:
         check(self.lib.rlo_program_iar(self.h, ctypes.byref(cfg), len(proposals), d(origin), d(pid), d(blob), d(doff),
                                        d(dlen)), "rlo_program_iar")
 
+    def program_send(self, origins, src, dst, slot, lens=None, ordered=False, log=False, hist=False, log_cap=0):
+        """rlo_program_send: message i (len(origins) of them) is a bcast from rank origins[i] of the lens[i] (None: slot)
+        bytes at src + i * slot, DEVICE memory; local rank lr's copy lands at dst + (lr * k + i) * slot, DEVICE memory.
+        src / dst: anything with data_ptr() and numel() * element_size() (a torch tensor), or an (int pointer, nbytes)
+        pair; src holds k * slot bytes, dst n_local * k * slot, both 16-B aligned.  ordered: one message in flight (a
+        total order; latencies_ticks() as for the latency program).  Only the hop kernel runs this program: a launch
+        that cannot run it raises."""
+        origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
+        k = int(origin.size)
+        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
+        if ln is not None and ln.size != k:
+            raise ValueError("program_send: %d lengths for %d messages" % (ln.size, k))
+        sp, sn = _dev_extent(src)
+        dp, dn = _dev_extent(dst)
+        if sp % 16 or dp % 16:
+            raise ValueError("program_send: src and dst must be 16-byte aligned")
+        if sn < k * slot or dn < self.n_local * k * slot:
+            raise ValueError("program_send: src holds %d bytes (needs %d), dst %d (needs %d)" %
+                             (sn, k * slot, dn, self.n_local * k * slot))
+        cfg = L.SendCfg()
+        cfg.k = k
+        cfg.origin = origin.ctypes.data
+        cfg.len = None if ln is None else ln.ctypes.data
+        cfg.src, cfg.dst = sp, dp
+        cfg.slot = slot
+        cfg.flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0) | (L.RLO_SEND_ORDERED if ordered else 0)
+        cfg.log_cap = log_cap
+        self._keep = [origin, ln, src, dst, cfg]
+        check(self.lib.rlo_program_send(self.h, ctypes.byref(cfg)), "rlo_program_send")
+        self._lat_rounds = k if ordered else 0
+
+    def bcast_tensor(self, origin, t, stream=None):
+        """Broadcast the contiguous CUDA tensor t (any dtype, any size) from rank `origin` of a one-part world through
+        the send program, in messages of at most 1008 bytes, on torch's current stream (or `stream`, a raw
+        hipStream_t): a kernel that produced t on that stream just before needs no synchronise.  Returns a tensor of
+        shape [n, *t.shape] and t's dtype: row r is rank r's copy (the origin's row is t itself, copied here)."""
+        import torch
+
+        if self.n_local != self.n:
+            raise ValueError("bcast_tensor: one-part worlds only")
+        if not (t.is_cuda and t.is_contiguous()):
+            raise ValueError("bcast_tensor: a contiguous tensor in device memory")
+        if not 0 <= origin < self.n:
+            raise ValueError("bcast_tensor: origin %d of %d ranks" % (origin, self.n))
+        n, nbytes = self.n, t.numel() * t.element_size()
+        if nbytes == 0:
+            return t.unsqueeze(0).repeat((n,) + (1,) * t.dim())
+        slot = min(1008, self.info["slot_stride"] - 16)
+        frags = send_fragments(nbytes, slot)
+        k = len(frags)
+        flat = t.reshape(-1).view(torch.uint8)
+        if nbytes == k * slot and flat.data_ptr() % 16 == 0:
+            src = flat
+        else:  # a padded staging copy: t is never read past its end
+            src = torch.empty(k * slot, dtype=torch.uint8, device=t.device)
+            src[:nbytes].copy_(flat)
+        dst = torch.empty((n, k * slot), dtype=torch.uint8, device=t.device)
+        self.program_send([origin] * k, src, dst, slot, lens=[f[1] for f in frags])
+        if stream is None:
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+        self.launch(stream=stream)
+        self.wait()
+        out = dst[:, :nbytes].contiguous().view(t.dtype).reshape((n,) + tuple(t.shape))
+        out[origin].copy_(t)
+        return out
+
     # ------------------------------------------------------------ run
     def launch(self, stream=None, no_reset=False):
         check(self.lib.rlo_launch_ex(self.h, stream, L.RLO_LAUNCH_NO_RESET if no_reset else 0), "rlo_launch")
@@ -262,6 +331,22 @@ class World:
         arr = (ctypes.c_uint32 * cap)()
         n = check(self.lib.rlo_timeline(self.h, arr, cap, ctypes.byref(stride)), "rlo_timeline")
         return np.array(arr[:n * stride.value], dtype=np.uint32).reshape(n, stride.value)
+
+
+def _dev_extent(x):
+    """(pointer, bytes) of a device buffer: an (int pointer, nbytes) pair, or anything with data_ptr() / numel() /
+    element_size() (a torch tensor)"""
+    if isinstance(x, (tuple, list)):
+        return int(x[0]), int(x[1])
+    return int(x.data_ptr()), int(x.numel()) * int(x.element_size())
+
+
+def send_fragments(nbytes, slot=1008):
+    """the (offset, len) fragments of at most `slot` bytes that cover nbytes, in order (only the last is short): the
+    messages World.bcast_tensor sends.  Pure Python, no GPU"""
+    if slot <= 0 or slot % 16 or slot > 1008:
+        raise ValueError("send_fragments: slot must be a multiple of 16 in 16 .. 1008")
+    return [(off, min(slot, nbytes - off)) for off in range(0, max(int(nbytes), 0), slot)]
 
 
 def pool_trim(what):
