@@ -389,6 +389,12 @@ int rlo_layout_plan(const rlo_plan_cfg_t* cfg, rlo_world_info_t* out);
 /* the storm program's payload length of bcasts 0..k-1 (rlo_storm_cfg_t len, len_max, seed): the
  * workload generator's host side, for byte accounting (no GPU) */
 int rlo_storm_lengths(uint64_t seed, uint64_t k, uint32_t len, uint32_t len_max, uint32_t* out);
+/* introspection (no GPU): the kernel instantiation a launch runs, by the pick functions the launch itself uses.
+ * kernel: 0 the progress kernel, 1 the hop kernel (as rlo_world_info_t.last_kernel); variant: 8 / 4 waves, 5 = 4 waves
+ * with bulk messages (progress only); mode: the launch's mode bits (rlo_device.hpp Mode); pend_hbm, sys_scope: as
+ * rlo_world_info_t.  out: the instantiation's template arguments -- progress {W, BULK, LL, PH, program mask}, hop
+ * {PH, SYS, LOC, SEND, 0}.  RLO_E_INVAL: no such kernel (the hop kernel's send program, or system scope, on one XCD) */
+int rlo_kernel_pick(int kernel, int variant, uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]);
 int rlo_host_bulk_stage(rlo_world_t* w, int rank, const void* data, uint64_t len, uint32_t timeout_us, uint32_t* q);
 int rlo_host_bulk_copy(rlo_world_t* w, int rank, const rlo_log_rec_t* ev, void* dst);
 

@@ -81,7 +81,7 @@ enum HopCnt : int {
 // caller's source buffer in device memory and every receiver writes to its place in the caller's destination buffer
 // (DESIGN.md 4.0.3).  Open loop (every rank originates its own messages as its out-rings take them) or, with MODE_LAT
 // set beside it, the latency program's closed loop (RLO_SEND_ORDERED).  No pending table, no one-XCD form: instantiated
-// for <false, false, false, true> and <false, true, false, true> only; every statement of it sits under
+// for the two scopes only (RLO_HOP_ROWS at the end of this file); every statement of it sits under
 // `if constexpr (SEND)`, so the other instantiations are what they were
 constexpr uint32_t kSendBurst = 4;  // open loop: originations per round at most, so taking ring messages is never starved
 template <bool PH, bool SYS, bool LOC, bool SEND = false>
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(&P.topo[lr]);
         uint32_t* dst = reinterpret_cast<uint32_t*>(&S.t);
         for (int i = lane; i < (int)(sizeof(RankTopo) / 4); i += 64) dst[i] = src[i];
-        // (the latency program never touches the table, and is launched without one: rlo_world.cpp hop_lds)
+        // (the latency program never touches the table, and is launched without one: rlo_world.cpp plan_launch)
         if (iar)
             for (int i = lane; i < P.n * (int)P.pend_slots; i += 64) pend[i] = PendState{0, 0, 0, 0, 0, 0};
         for (int i = lane; i < kHistBins; i += 64) S.hist[i] = 0;
@@ -544,7 +544,7 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
             const uint32_t off = first != 0u && first != mine ? 0x10001u : 1u;
             atomicAdd(P.xcd_word + 1, off);
             uint32_t v = 0;
-            for (uint32_t s = 0; s < (1u << 22); s++) {  // bounded: every rank-wave is co-resident (hop_eligible)
+            for (uint32_t s = 0; s < (1u << 22); s++) {  // bounded: every rank-wave is co-resident (plan_launch)
                 v = __hip_atomic_load(P.xcd_word + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if ((v & 0xFFFFu) >= P.n_local) break;
             }
@@ -967,63 +967,64 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
 }  // namespace rlo
 
 // C-ABI launch shims (rlo_world.cpp): one 64-thread workgroup per local rank, the pending table in dynamic LDS
-// (dyn_lds bytes) or, with Params.pend_hbm, in HBM (the PH instantiation); system-scope worlds run the SYS one
-template <bool PH, bool SYS, bool LOC = false, bool SEND = false>
-static hipError_t hop_grant(size_t dyn_lds) {
-    static size_t granted = 0;
-    if (dyn_lds > granted) {
-        hipError_t e = hipFuncSetAttribute((const void*)rlo::rlo_hop_kernel<PH, SYS, LOC, SEND>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
+// (dyn_lds bytes) or, with Params.pend_hbm, in HBM (the PH instantiation); system-scope worlds run the SYS one.
+//
+// THE instantiations of rlo_hop_kernel<PH, SYS, LOC, SEND>: the launch pointer, the dynamic-LDS grant and the occupancy
+// query of each come from its row.  The one-XCD form (LOC) has no system scope, the send program (SEND) no pending
+// table and no one-XCD form.  (Rows in the order the device code has always been emitted in.)
+#define RLO_HOP_ROWS(X)                                                                          \
+    X(false, true, false, true) X(false, false, false, true) X(true, false, true, false)         \
+    X(false, false, true, false) X(true, true, false, false) X(true, false, false, false)        \
+    X(false, true, false, false) X(false, false, false, false)
+
+struct HopRow { bool ph, sys, loc, send; void (*kernel)(rlo::Params); };
+#define X(PH, SYS, LOC, SEND) {PH, SYS, LOC, SEND, rlo::rlo_hop_kernel<PH, SYS, LOC, SEND>},
+static const HopRow kHopRows[] = {RLO_HOP_ROWS(X)};
+#undef X
+constexpr int kHopN = (int)(sizeof kHopRows / sizeof kHopRows[0]);
+static size_t g_hop_granted[kHopN];  // dynamic LDS granted to a row's kernel so far
+
+static hipError_t hop_grant(int row, size_t dyn_lds) {
+    if (dyn_lds > g_hop_granted[row]) {
+        hipError_t e = hipFuncSetAttribute((const void*)kHopRows[row].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
         if (e != hipSuccess) return e;
-        granted = dyn_lds;
+        g_hop_granted[row] = dyn_lds;
     }
     return hipSuccess;
 }
-template <bool PH, bool SYS, bool LOC = false, bool SEND = false>
-static hipError_t hop_launch(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream) {
-    hipError_t e = hop_grant<PH, SYS, LOC, SEND>(dyn_lds);
+
+// The row a launch runs, from (Params.mode, a pending table in HBM, Params.sys_scope): no HIP call.  The send program
+// has no pending table, whatever the world's.  -1: no such kernel (the send program, or a system-scope world, on one
+// XCD).  out (may be null): {PH, SYS, LOC, SEND}
+extern "C" int rlo_pick_hop(uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[4]) {
+    const bool send = (mode & rlo::MODE_SEND) != 0, loc = (mode & rlo::MODE_XCD1) != 0;  // (RLO_PART_ONE_XCD)
+    const bool sys = sys_scope != 0, ph = pend_hbm && !send;
+    for (int i = 0; i < kHopN; i++) {
+        const HopRow& r = kHopRows[i];
+        if (r.ph != ph || r.sys != sys || r.loc != loc || r.send != send) continue;
+        if (out) out[0] = r.ph, out[1] = r.sys, out[2] = r.loc, out[3] = r.send;
+        return i;
+    }
+    return -1;
+}
+
+// launches row `row` (rlo_pick_hop)
+extern "C" hipError_t rlo_launch_hop(int row, const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream) {
+    if (row < 0 || row >= kHopN) return hipErrorInvalidValue;
+    const HopRow& r = kHopRows[row];
+    // the send program's launch takes no dynamic LDS; the one-XCD form needs its rendezvous word
+    if (r.send && (dyn_lds != 0 || !p->send_src || !p->send_dst)) return hipErrorInvalidValue;
+    if (r.loc && !p->xcd_word) return hipErrorInvalidValue;
+    hipError_t e = hop_grant(row, dyn_lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((rlo::rlo_hop_kernel<PH, SYS, LOC, SEND>), dim3(LOC ? 8 * blocks : blocks), dim3(64), dyn_lds, stream, *p);
+    hipLaunchKernelGGL(r.kernel, dim3(r.loc ? 8 * blocks : blocks), dim3(64), dyn_lds, stream, *p);
     return hipGetLastError();
 }
-template <bool PH, bool SYS, bool SEND = false>
-static hipError_t hop_occ(int* blocks, size_t dyn_lds) {
-    hipError_t e = hop_grant<PH, SYS, false, SEND>(dyn_lds);
-    if (e != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, rlo::rlo_hop_kernel<PH, SYS, false, SEND>, 64, dyn_lds);
-}
 
-extern "C" hipError_t rlo_launch_hop(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream) {
-    const bool ph = p->pend_hbm != nullptr, sys = p->sys_scope != 0;
-    if (p->mode & rlo::MODE_SEND) {  // the send program: no one-XCD form, no pending table (its launch takes no dynamic LDS)
-        if ((p->mode & rlo::MODE_XCD1) || dyn_lds != 0 || !p->send_src || !p->send_dst) return hipErrorInvalidValue;
-        return sys ? hop_launch<false, true, false, true>(p, blocks, 0, stream) : hop_launch<false, false, false, true>(p, blocks, 0, stream);
-    }
-    if ((p->mode & rlo::MODE_XCD1) && (sys || !p->xcd_word)) return hipErrorInvalidValue;  // (the rendezvous word)
-    if (p->mode & rlo::MODE_XCD1)  // RLO_PART_ONE_XCD
-        return ph ? hop_launch<true, false, true>(p, blocks, dyn_lds, stream) : hop_launch<false, false, true>(p, blocks, dyn_lds, stream);
-    return ph ? (sys ? hop_launch<true, true>(p, blocks, dyn_lds, stream) : hop_launch<true, false>(p, blocks, dyn_lds, stream))
-              : (sys ? hop_launch<false, true>(p, blocks, dyn_lds, stream) : hop_launch<false, false>(p, blocks, dyn_lds, stream));
-}
-
-// the smaller of the two scope instantiations' answers (the world's scope is known only at launch)
-extern "C" hipError_t rlo_occupancy_hop(int* blocks, size_t dyn_lds, int ph) {
-    int a = 0, b = 0;
-    hipError_t e = ph ? hop_occ<true, false>(&a, dyn_lds) : hop_occ<false, false>(&a, dyn_lds);
+// workgroups per CU of row `row`, the instantiation a launch runs (its scope is known then), at dyn_lds bytes of dynamic LDS
+extern "C" hipError_t rlo_occupancy_hop(int row, int* blocks, size_t dyn_lds) {
+    if (row < 0 || row >= kHopN) return hipErrorInvalidValue;
+    hipError_t e = hop_grant(row, dyn_lds);
     if (e != hipSuccess) return e;
-    e = ph ? hop_occ<true, true>(&b, dyn_lds) : hop_occ<false, true>(&b, dyn_lds);
-    if (e != hipSuccess) return e;
-    *blocks = a < b ? a : b;
-    return hipSuccess;
-}
-
-// the same for the send program's two instantiations
-extern "C" hipError_t rlo_occupancy_hop_send(int* blocks) {
-    int a = 0, b = 0;
-    hipError_t e = hop_occ<false, false, true>(&a, 0);
-    if (e != hipSuccess) return e;
-    e = hop_occ<false, true, true>(&b, 0);
-    if (e != hipSuccess) return e;
-    *blocks = a < b ? a : b;
-    return hipSuccess;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kHopRows[row].kernel, 64, dyn_lds);
 }

@@ -826,7 +826,7 @@ template <int W, bool BULK, bool LL, bool PH = false, uint32_t PM = kPmAll>
 __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     // PM: the programs this instantiation can run (kPm*): a mode bit PM lacks is a compile-time 0, so the code of
     // the other programs drops out of it (the latency and iar programs' doorbell kernels: fewer live values on the
-    // hop path).  rlo_launch_progress picks the instantiation by Params.mode
+    // hop path).  rlo_pick_progress picks the instantiation by Params.mode
 #define PMODE(x) ((PM & (uint32_t)(x)) ? (P.mode & (uint32_t)(x)) : 0u)
     // pulled payloads (Params.pull) exist only in the 4-wave kernel without bulk messages (slots beyond
     // the small copy path); compiled out of the others
@@ -951,7 +951,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     if constexpr (PH) VM_DRAIN();  // the table's zeros land before any wave (the doorbell pass) reads them
     BAR();
     if (host && tid == 0) pub64_sys(&hctl[kHctlState], 1ull);  // serving (rlo_host_wait_started)
-    // a program that holds proposals in a PH world runs the PH instantiation (rlo_launch_progress)
+    // a program that holds proposals in a PH world runs the PH instantiation (rlo_pick_progress)
     if (!PH && P.pend_hbm && (PMODE(MODE_IAR | MODE_HOST)) && tid == 0) set_error(S, P, ERR_HOST_CMD, 0x9E4Du);
     const uint64_t t_start = now_ticks();
     unsigned long long acc_sum = 0;  // checksum of delivered bcast chunks (this thread's share)
@@ -3351,90 +3351,79 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
 // bulk messages (mover workgroups + mixed storm lengths); the Shared / LDS layout depends on it.  A
 // program with doorbells (MODE_LL: latency, IAR, host service) runs the doorbell instantiation of its
 // variant, the storm the one without (its registers untouched)
-template <int W, bool B, bool L, bool H = false, uint32_t PM = rlo::kPmAll>
-static hipError_t grant_dyn_lds(size_t dyn_lds) {
-    static size_t granted = 0;
-    if (dyn_lds > granted) {  // > 64 KiB of dynamic LDS must be requested explicitly
-        hipError_t e = hipFuncSetAttribute((const void*)rlo::rlo_progress_kernel<W, B, L, H, PM>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
+//
+// THE instantiations of rlo_progress_kernel<W, BULK, LL, PH, PM>: the launch pointer, the dynamic-LDS grant and the
+// occupancy query of each come from its row, and the Makefile's SPILL_PRODUCT must hold a budget for exactly these
+// (the product build fails otherwise).  Beside the general kernel of every <W, BULK, LL, PH> (kPmAll), the kernels of
+// the device programs the bench times are specialised by program (PM): 8 waves -- the storm (no doorbells), the
+// latency program and the iar program (doorbells; the iar one with the LDS or the HBM pending table); bulk worlds --
+// the latency program (C3) and the storm (C5); and the host service the drop-in runs (doorbells; every variant, LDS
+// or HBM tables).  PH: programs that hold proposals in a world with HBM pending tables (no bulk worlds: their N x B
+// bound keeps the table small).  (Rows in the order the device code has always been emitted in.)
+#define RLO_PROGRESS_ROWS(X)                                                                                     \
+    X(8, false, true, true, kPmIar) X(8, false, true, true, kPmHost) X(8, false, true, true, kPmAll)              \
+    X(8, false, false, true, kPmAll)                                                                             \
+    X(4, false, true, true, kPmHost) X(4, false, true, true, kPmAll) X(4, false, false, true, kPmAll)             \
+    X(8, false, true, false, kPmLat) X(8, false, true, false, kPmIar) X(8, false, false, false, kPmStorm)         \
+    X(8, false, true, false, kPmHost) X(8, false, true, false, kPmAll) X(8, false, false, false, kPmAll)          \
+    X(4, true, true, false, kPmLat) X(4, true, false, false, kPmStorm) X(4, true, true, false, kPmHost)           \
+    X(4, true, true, false, kPmAll) X(4, true, false, false, kPmAll)                                              \
+    X(4, false, true, false, kPmHost) X(4, false, true, false, kPmAll) X(4, false, false, false, kPmAll)
+
+struct ProgressRow { int w; bool bulk, ll, ph; uint32_t pm; void (*kernel)(rlo::Params); };
+#define X(W, B, L, H, PM) {W, B, L, H, rlo::PM, rlo::rlo_progress_kernel<W, B, L, H, rlo::PM>},
+static const ProgressRow kProgressRows[] = {RLO_PROGRESS_ROWS(X)};
+#undef X
+constexpr int kProgressN = (int)(sizeof kProgressRows / sizeof kProgressRows[0]);
+static size_t g_progress_granted[kProgressN];  // dynamic LDS granted to a row's kernel so far
+
+static int progress_row(int w, bool bulk, bool ll, bool ph, uint32_t pm) {
+    for (int i = 0; i < kProgressN; i++) {
+        const ProgressRow& r = kProgressRows[i];
+        if (r.w == w && r.bulk == bulk && r.ll == ll && r.ph == ph && r.pm == pm) return i;
+    }
+    return -1;
+}
+
+static hipError_t progress_grant(int row, size_t dyn_lds) {
+    if (dyn_lds > g_progress_granted[row]) {  // > 64 KiB of dynamic LDS must be requested explicitly
+        hipError_t e = hipFuncSetAttribute((const void*)kProgressRows[row].kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)dyn_lds);
         if (e != hipSuccess) return e;
-        granted = dyn_lds;
+        g_progress_granted[row] = dyn_lds;
     }
     return hipSuccess;
 }
 
-template <int W, bool B, bool L, bool H = false, uint32_t PM = rlo::kPmAll>
-static hipError_t launch_v(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream) {
-    hipError_t e = grant_dyn_lds<W, B, L, H, PM>(dyn_lds);
+// The row a launch runs, from (variant, Params.mode, a pending table in HBM): no HIP call.  The kernel specialised
+// for the launch's one program (the host service: MODE_HOST with or without MODE_IAR) where the table has it for
+// this <W, BULK, LL, PH>, else the general one.  out (may be null): {W, BULK, LL, PH, PM}
+extern "C" int rlo_pick_progress(int variant, uint32_t mode, int pend_hbm, uint32_t out[5]) {
+    const int w = variant == 8 ? 8 : 4;
+    const bool bulk = variant == 5, ll = (mode & rlo::MODE_LL) != 0;
+    const bool ph = pend_hbm && (mode & (rlo::MODE_IAR | rlo::MODE_HOST)) != 0 && !bulk;
+    const uint32_t prog = mode & (rlo::MODE_STORM | rlo::MODE_LAT | rlo::MODE_IAR | rlo::MODE_HOST);
+    const uint32_t want = (prog & rlo::MODE_HOST) ? rlo::kPmHost
+                          : prog == rlo::MODE_LAT ? rlo::kPmLat
+                          : prog == rlo::MODE_IAR ? rlo::kPmIar
+                          : prog == rlo::MODE_STORM ? rlo::kPmStorm
+                                                    : rlo::kPmAll;
+    int row = progress_row(w, bulk, ll, ph, want);
+    if (row < 0) row = progress_row(w, bulk, ll, ph, rlo::kPmAll);
+    if (row >= 0 && out) {
+        const ProgressRow& r = kProgressRows[row];
+        out[0] = (uint32_t)r.w, out[1] = r.bulk, out[2] = r.ll, out[3] = r.ph, out[4] = r.pm;
+    }
+    return row;
+}
+
+// launches row `row` (rlo_pick_progress)
+extern "C" hipError_t rlo_launch_progress(int row, const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream) {
+    if (row < 0 || row >= kProgressN) return hipErrorInvalidValue;
+    hipError_t e = progress_grant(row, dyn_lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((rlo::rlo_progress_kernel<W, B, L, H, PM>), dim3(blocks), dim3(64 * W), dyn_lds, stream, *p);
+    hipLaunchKernelGGL(kProgressRows[row].kernel, dim3(blocks), dim3(64 * kProgressRows[row].w), dyn_lds, stream, *p);
     return hipGetLastError();
-}
-
-template <int W, bool B, bool L, bool H = false, uint32_t PM = rlo::kPmAll>
-static hipError_t occ_one(int* blocks, size_t dyn_lds) {
-    hipError_t e = grant_dyn_lds<W, B, L, H, PM>(dyn_lds);
-    if (e != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, rlo::rlo_progress_kernel<W, B, L, H, PM>, 64 * W, dyn_lds);
-}
-
-// the occupancy of <W, B, L, H> = the least over its general instantiation and every program-specialised one that
-// rlo_launch_progress launches for it (PMs...): co-residency is decided from this answer, so a specialised kernel
-// that fell below its general twin would leave workgroups of a persistent launch unscheduled
-template <int W, bool B, bool L, bool H, uint32_t... PMs>
-static hipError_t occ_v(int* blocks, size_t dyn_lds) {
-    hipError_t e = occ_one<W, B, L, H>(blocks, dyn_lds);
-    if (e != hipSuccess) return e;
-    const hipError_t es[] = {hipSuccess, [&]() -> hipError_t {
-        int b = 0;
-        const hipError_t r = occ_one<W, B, L, H, PMs>(&b, dyn_lds);
-        if (r == hipSuccess && b < *blocks) *blocks = b;
-        return r;
-    }()...};
-    for (hipError_t x : es)
-        if (x != hipSuccess) return x;
-    return hipSuccess;
-}
-
-// programs that hold proposals in a world with HBM pending tables run the PH instantiations (no bulk
-// worlds: their N x B bound keeps the table small)
-static bool wants_ph(const rlo::Params* p) {
-    return p->pend_hbm != nullptr && (p->mode & (rlo::MODE_IAR | rlo::MODE_HOST)) != 0;
-}
-
-// The kernels of the device programs the bench times are specialised by program (PM): 8 waves -- the storm
-// (no doorbells), the latency program and the iar program (doorbells; the iar one with the LDS or the HBM
-// pending table); bulk worlds -- the latency program (C3) and the storm (C5); and the host service the drop-in
-// runs (doorbells; every variant, LDS or HBM tables).  The host's occupancy answer (rlo_occupancy*) is the least over the
-// general instantiation and these; the Makefile guard holds every 8-wave instantiation to 2 waves per SIMD.
-extern "C" hipError_t rlo_launch_progress(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream, int variant) {
-    const bool ll = (p->mode & rlo::MODE_LL) != 0;
-    const uint32_t prog = p->mode & (rlo::MODE_STORM | rlo::MODE_LAT | rlo::MODE_IAR | rlo::MODE_HOST);
-    const bool hll = ll && (prog & rlo::MODE_HOST) != 0;  // the drop-in's host service (HOST | IAR) with doorbells
-    if (wants_ph(p) && variant != 5) {
-        if (variant == 8) {
-            if (ll && prog == rlo::MODE_IAR) return launch_v<8, false, true, true, rlo::kPmIar>(p, blocks, dyn_lds, stream);
-            if (hll) return launch_v<8, false, true, true, rlo::kPmHost>(p, blocks, dyn_lds, stream);
-            return ll ? launch_v<8, false, true, true>(p, blocks, dyn_lds, stream) : launch_v<8, false, false, true>(p, blocks, dyn_lds, stream);
-        }
-        if (hll) return launch_v<4, false, true, true, rlo::kPmHost>(p, blocks, dyn_lds, stream);
-        return ll ? launch_v<4, false, true, true>(p, blocks, dyn_lds, stream) : launch_v<4, false, false, true>(p, blocks, dyn_lds, stream);
-    }
-    if (variant == 8) {
-        if (ll && prog == rlo::MODE_LAT) return launch_v<8, false, true, false, rlo::kPmLat>(p, blocks, dyn_lds, stream);
-        if (ll && prog == rlo::MODE_IAR) return launch_v<8, false, true, false, rlo::kPmIar>(p, blocks, dyn_lds, stream);
-        if (!ll && prog == rlo::MODE_STORM) return launch_v<8, false, false, false, rlo::kPmStorm>(p, blocks, dyn_lds, stream);
-        if (hll) return launch_v<8, false, true, false, rlo::kPmHost>(p, blocks, dyn_lds, stream);
-        return ll ? launch_v<8, false, true>(p, blocks, dyn_lds, stream) : launch_v<8, false, false>(p, blocks, dyn_lds, stream);
-    }
-    if (variant == 5) {  // bulk worlds: the C3 leg's latency program (doorbells) and the C5 storm, specialised too
-        if (ll && prog == rlo::MODE_LAT) return launch_v<4, true, true, false, rlo::kPmLat>(p, blocks, dyn_lds, stream);
-        if (!ll && prog == rlo::MODE_STORM) return launch_v<4, true, false, false, rlo::kPmStorm>(p, blocks, dyn_lds, stream);
-        if (hll) return launch_v<4, true, true, false, rlo::kPmHost>(p, blocks, dyn_lds, stream);
-        return ll ? launch_v<4, true, true>(p, blocks, dyn_lds, stream) : launch_v<4, true, false>(p, blocks, dyn_lds, stream);
-    }
-    if (hll) return launch_v<4, false, true, false, rlo::kPmHost>(p, blocks, dyn_lds, stream);
-    return ll ? launch_v<4, false, true>(p, blocks, dyn_lds, stream) : launch_v<4, false, false>(p, blocks, dyn_lds, stream);
 }
 
 extern "C" size_t rlo_kernel_static_lds(int variant) {
@@ -3443,21 +3432,25 @@ extern "C" size_t rlo_kernel_static_lds(int variant) {
     return sizeof(rlo::Shared<4, false>);
 }
 
-// variant | RLO_VARIANT_PH (16): the PH instantiation of variant 8 / 4
-extern "C" hipError_t rlo_occupancy(int* blocks, size_t dyn_lds, int variant) {
-    if (variant == (8 | 16)) return occ_v<8, false, false, true>(blocks, dyn_lds);
-    if (variant == (4 | 16)) return occ_v<4, false, false, true>(blocks, dyn_lds);
-    if (variant == 8) return occ_v<8, false, false, false, rlo::kPmStorm>(blocks, dyn_lds);
-    if (variant == 5) return occ_v<4, true, false, false, rlo::kPmStorm>(blocks, dyn_lds);
-    return occ_v<4, false, false, false>(blocks, dyn_lds);
-}
-
-// the doorbell instantiation of a variant: the 4-wave ones may take more than 256 registers (one wave
-// per SIMD: worlds whose ranks have a CU each), so a world gets doorbells only where this answer covers it
-extern "C" hipError_t rlo_occupancy_ll(int* blocks, size_t dyn_lds, int variant) {
-    if (variant == (8 | 16)) return occ_v<8, false, true, true, rlo::kPmIar, rlo::kPmHost>(blocks, dyn_lds);
-    if (variant == (4 | 16)) return occ_v<4, false, true, true, rlo::kPmHost>(blocks, dyn_lds);
-    if (variant == 8) return occ_v<8, false, true, false, rlo::kPmLat, rlo::kPmIar, rlo::kPmHost>(blocks, dyn_lds);
-    if (variant == 5) return occ_v<4, true, true, false, rlo::kPmLat, rlo::kPmHost>(blocks, dyn_lds);
-    return occ_v<4, false, true, false, rlo::kPmHost>(blocks, dyn_lds);
+// Workgroups per CU of `variant` (| RLO_VARIANT_PH (16): the PH instantiations of variant 8 / 4), with doorbells (ll)
+// or without: the least answer over every row of that <W, BULK, LL, PH>, the general kernel and the program-specialised
+// ones alike.  Co-residency is decided from this answer, so a specialised kernel that fell below its general twin
+// would leave workgroups of a persistent launch unscheduled.  The 4-wave doorbell kernels may take more
+// than 256 registers (one wave per SIMD: worlds whose ranks have a CU each), so a world gets doorbells only where
+// the ll answer covers it
+extern "C" hipError_t rlo_occupancy(int* blocks, size_t dyn_lds, int variant, int ll) {
+    const int v = variant & ~16, w = v == 8 ? 8 : 4;
+    int least = -1;
+    for (int i = 0; i < kProgressN; i++) {
+        const ProgressRow& r = kProgressRows[i];
+        if (r.w != w || r.bulk != (v == 5) || r.ll != (ll != 0) || r.ph != ((variant & 16) != 0)) continue;
+        int b = 0;
+        hipError_t e = progress_grant(i, dyn_lds);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, r.kernel, 64 * r.w, dyn_lds);
+        if (e != hipSuccess) return e;
+        if (least < 0 || b < least) least = b;
+    }
+    if (least < 0) return hipErrorInvalidValue;
+    *blocks = least;
+    return hipSuccess;
 }

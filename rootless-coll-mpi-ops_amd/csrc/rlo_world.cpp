@@ -26,14 +26,15 @@
 #include "rlo_hip.h"
 #include "rlo_shm.hpp"
 
-// variant: 8 = 8-wave, 4 = 4-wave, 5 = 4-wave with bulk messages (rlo_kernel.hip)
-extern "C" hipError_t rlo_launch_progress(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream, int variant);
+// variant: 8 = 8-wave, 4 = 4-wave, 5 = 4-wave with bulk messages (rlo_kernel.hip).  row: an instantiation of the
+// kernel, as its pick function (pure: no HIP call) returns it; -1: none
+extern "C" int rlo_pick_progress(int variant, uint32_t mode, int pend_hbm, uint32_t out[5]);
+extern "C" hipError_t rlo_launch_progress(int row, const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream);
 extern "C" size_t rlo_kernel_static_lds(int variant);
-extern "C" hipError_t rlo_occupancy(int* blocks, size_t dyn_lds, int variant);
-extern "C" hipError_t rlo_occupancy_ll(int* blocks, size_t dyn_lds, int variant);
-extern "C" hipError_t rlo_launch_hop(const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream);
-extern "C" hipError_t rlo_occupancy_hop(int* blocks, size_t dyn_lds, int ph);
-extern "C" hipError_t rlo_occupancy_hop_send(int* blocks);
+extern "C" hipError_t rlo_occupancy(int* blocks, size_t dyn_lds, int variant, int ll);
+extern "C" int rlo_pick_hop(uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[4]);
+extern "C" hipError_t rlo_launch_hop(int row, const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream);
+extern "C" hipError_t rlo_occupancy_hop(int row, int* blocks, size_t dyn_lds);
 
 static_assert(sizeof(rlo_rank_stats_t) == sizeof(rlo::RankStats), "stats ABI");
 static_assert(sizeof(rlo_log_rec_t) == sizeof(rlo::LogRec), "log ABI");
@@ -650,7 +651,7 @@ constexpr size_t kLdsPerCU = 163840;  // 160 KiB per CU (MI355X_MICROARCH.md)
 
 int occ_device(int variant, bool ll, size_t dyn_lds) {
     int b = 0;
-    if ((ll ? rlo_occupancy_ll(&b, dyn_lds, variant) : rlo_occupancy(&b, dyn_lds, variant)) != hipSuccess) return 0;
+    if (rlo_occupancy(&b, dyn_lds, variant, ll) != hipSuccess) return 0;
     return b;
 }
 // no GPU: LDS (512-B allocation granules), 32 waves per CU, and the waves per SIMD every instantiation is
@@ -807,6 +808,38 @@ void build_topo(rlo_world* w) {
             t.vout_bell[ed.k] = (uint64_t)(uintptr_t)(w->pc[ps] + L.vbell[ed.src] + 2 * ed.j);
         }
     }
+}
+
+// A program's schedule as its kernels read it: per LOCAL rank (the kernels index by workgroup) the messages it
+// originates, in order -- local rank lr's are idx[off[lr] .. off[lr + 1]) -- and expect[lr] = k - its own, the
+// messages of other ranks it must see.  origin_of(i): the world rank that originates message i < k; place(at, i),
+// in the order of i: message i took place `at` of idx (a program's tables parallel to idx).  An empty idx is padded
+// to one element (no zero-byte uploads)
+template <class Off>
+struct OwnLists { std::vector<Off> off; std::vector<uint32_t> idx; std::vector<int64_t> expect; };
+template <class Off, class Origin, class Place = void (*)(size_t, int64_t)>
+OwnLists<Off> own_lists(const rlo_world* w, int64_t k, Origin origin_of, Place place = [](size_t, int64_t) {}) {
+    const int nl = w->nl, rb = w->rb;
+    OwnLists<Off> o{std::vector<Off>(nl + 1, 0), {}, std::vector<int64_t>(nl)};
+    std::vector<int32_t> lr((size_t)k);  // message i's local rank, -1: another part's
+    for (int64_t i = 0; i < k; i++) {
+        const int64_t r = (int64_t)origin_of(i) - rb;
+        lr[i] = r >= 0 && r < nl ? (int32_t)r : -1;
+        if (lr[i] >= 0) o.off[lr[i] + 1]++;
+    }
+    for (int r = 0; r < nl; r++) {
+        o.expect[r] = k - (int64_t)o.off[r + 1];
+        o.off[r + 1] += o.off[r];
+    }
+    o.idx.assign(std::max<size_t>((size_t)o.off[nl], 1), 0);
+    std::vector<Off> fill(o.off.begin(), o.off.end() - 1);
+    for (int64_t i = 0; i < k; i++)
+        if (lr[i] >= 0) {
+            const size_t at = (size_t)fill[lr[i]]++;
+            o.idx[at] = (uint32_t)i;
+            place(at, i);
+        }
+    return o;
 }
 
 }  // namespace
@@ -1429,6 +1462,29 @@ static int setup_log(rlo_world* w, uint32_t flags, uint32_t log_cap, bool payloa
     return RLO_OK;
 }
 
+static uint32_t flag_modes(uint32_t flags) {
+    return ((flags & RLO_FLAG_HIST) ? rlo::MODE_HIST : 0u) | ((flags & RLO_FLAG_PROF) ? rlo::MODE_PROF : 0u);
+}
+
+// the latency program's closed loop (the ordered send program's too): round word, delivery counts, completion ticks
+static int closed_loop(rlo_world* w, uint32_t rounds) {
+    rlo::Params& P = w->P;
+    if (w->d_lat_count.alloc(rounds) || w->d_lat_out.alloc(rounds) || w->d_lat_round.alloc(1) || w->d_lat_obs.alloc(rounds))
+        return RLO_E_HIP;
+    P.lat_rounds = rounds;
+    P.lat_count = w->d_lat_count.p;
+    P.lat_out = w->d_lat_out.p;
+    P.lat_round = w->d_lat_round.p;
+    P.lat_obs = w->d_lat_obs.p;
+    if (w->L.nparts != 1) {  // sharded: the round word and counts are part 0's copy, peer-mapped (rlo_device.hpp kLatWords)
+        uint64_t* blk = w->pc[0] + w->L.lat_base[0];
+        P.lat_round = reinterpret_cast<uint32_t*>(blk);
+        P.lat_count = reinterpret_cast<uint32_t*>(blk + 16);
+    }
+    w->lat_rounds = rounds;
+    return RLO_OK;
+}
+
 int rlo_program_storm(rlo_world_t* w, const rlo_storm_cfg_t* cfg) {
     if (!w || !cfg || cfg->k < 0 || cfg->k > 0xFFFFFFFFll || cfg->order > RLO_ORDER_SLOTS) return RLO_E_INVAL;
     const uint32_t hi = std::max(cfg->len, cfg->len_max);
@@ -1438,25 +1494,13 @@ int rlo_program_storm(rlo_world_t* w, const rlo_storm_cfg_t* cfg) {
     if (!w->connected) return RLO_E_NOTCONNECTED;
     base_params(w);
     rlo::Params& P = w->P;
-    const int n = w->L.n, nl = w->nl, rb = w->rb;
+    const int n = w->L.n;
     // the whole world's schedule is a pure function of (seed, k): each part keeps its own ranks'
-    std::vector<int64_t> off(nl + 1, 0), expect(nl, 0), per(n, 0);
-    std::vector<uint32_t> org((size_t)std::max<int64_t>(cfg->k, 1));
-    for (int64_t b = 0; b < cfg->k; b++) {
-        org[b] = cfg->order == RLO_ORDER_SLOTS ? (uint32_t)(b % n)
-                                               : (uint32_t)(splitmix64(cfg->seed + (uint64_t)b) % (uint64_t)n);
-        per[org[b]]++;
-        if ((int)org[b] >= rb && (int)org[b] < rb + nl) off[org[b] - rb + 1]++;
-    }
-    for (int r = 0; r < nl; r++) off[r + 1] += off[r];
-    std::vector<uint32_t> ids((size_t)std::max<int64_t>(off[nl], 1));
-    std::vector<int64_t> fill(off.begin(), off.end() - 1);
-    for (int64_t b = 0; b < cfg->k; b++)
-        if ((int)org[b] >= rb && (int)org[b] < rb + nl) ids[fill[org[b] - rb]++] = (uint32_t)b;
-    for (int r = 0; r < nl; r++) expect[r] = cfg->k - per[rb + r];
-    if (w->d_sched_off.upload(off) || w->d_sched_ids.upload(ids) || w->d_expect_bcast.upload(expect)) return RLO_E_HIP;
-    P.mode = rlo::MODE_STORM | ((cfg->flags & RLO_FLAG_HIST) ? rlo::MODE_HIST : 0u) |
-             ((cfg->flags & RLO_FLAG_PROF) ? rlo::MODE_PROF : 0u);
+    const auto own = own_lists<int64_t>(w, cfg->k, [&](int64_t b) {
+        return cfg->order == RLO_ORDER_SLOTS ? (uint32_t)(b % n) : (uint32_t)(splitmix64(cfg->seed + (uint64_t)b) % (uint64_t)n);
+    });
+    if (w->d_sched_off.upload(own.off) || w->d_sched_ids.upload(own.idx) || w->d_expect_bcast.upload(own.expect)) return RLO_E_HIP;
+    P.mode = rlo::MODE_STORM | flag_modes(cfg->flags);
     P.seed = cfg->seed;
     P.len = cfg->len;
     P.len_lo = cfg->len;
@@ -1484,42 +1528,19 @@ int rlo_program_latency(rlo_world_t* w, uint32_t rounds, uint32_t len, uint64_t 
     rlo::Params& P = w->P;
     const int n = w->L.n;
     std::vector<int32_t> org(rounds);
-    std::vector<int64_t> expect(w->nl, 0);  // per LOCAL rank (the kernel indexes by workgroup)
     for (uint32_t i = 0; i < rounds; i++) org[i] = (int32_t)(splitmix64(seed + i) % (uint64_t)n);
-    for (int lr = 0; lr < w->nl; lr++)
-        for (uint32_t i = 0; i < rounds; i++) expect[lr] += org[i] != w->rb + lr;
     // per local rank the rounds it originates, in order (the kernel prefetches the next one)
-    std::vector<uint32_t> own_off(w->nl + 1, 0), own;
-    for (int lr = 0; lr < w->nl; lr++) {
-        for (uint32_t i = 0; i < rounds; i++)
-            if (org[i] == w->rb + lr) own.push_back(i);
-        own_off[lr + 1] = (uint32_t)own.size();
-    }
-    if (own.empty()) own.push_back(0);
-    if (w->d_lat_own_off.upload(own_off) || w->d_lat_own.upload(own)) return RLO_E_HIP;
-    if (w->d_lat_origin.upload(org) || w->d_expect_bcast.upload(expect) || w->d_lat_count.alloc(rounds) ||
-        w->d_lat_out.alloc(rounds) || w->d_lat_round.alloc(1) || w->d_lat_obs.alloc(rounds))
-        return RLO_E_HIP;
-    P.mode = rlo::MODE_LAT | ((flags & RLO_FLAG_HIST) ? rlo::MODE_HIST : 0u) | ((flags & RLO_FLAG_PROF) ? rlo::MODE_PROF : 0u) |
-             ll_mode(w, len);
+    const auto own = own_lists<uint32_t>(w, rounds, [&](int64_t i) { return org[i]; });
+    if (w->d_lat_own_off.upload(own.off) || w->d_lat_own.upload(own.idx)) return RLO_E_HIP;
+    if (w->d_lat_origin.upload(org) || w->d_expect_bcast.upload(own.expect) || closed_loop(w, rounds)) return RLO_E_HIP;
+    P.mode = rlo::MODE_LAT | flag_modes(flags) | ll_mode(w, len);
     P.len = len;
     P.seed = seed;
-    P.lat_rounds = rounds;
     P.hop_chunks = (rlo::kHdr + len + 15u) / 16u;
     P.lat_origin = w->d_lat_origin.p;
-    P.lat_count = w->d_lat_count.p;
-    P.lat_out = w->d_lat_out.p;
-    P.lat_round = w->d_lat_round.p;
-    P.lat_obs = w->d_lat_obs.p;
-    if (w->L.nparts != 1) {
-        uint64_t* blk = w->pc[0] + w->L.lat_base[0];
-        P.lat_round = reinterpret_cast<uint32_t*>(blk);
-        P.lat_count = reinterpret_cast<uint32_t*>(blk + 16);
-    }
     P.lat_own_off = w->d_lat_own_off.p;
     P.lat_own = w->d_lat_own.p;
     P.expect_bcast = w->d_expect_bcast.p;
-    w->lat_rounds = rounds;
     w->tl_rows = 0;
     P.tl = nullptr;
     P.tl_rounds = 0;
@@ -1561,29 +1582,17 @@ int rlo_program_send(rlo_world_t* w, const rlo_send_cfg_t* cfg) {
     if (!w->connected) return RLO_E_NOTCONNECTED;
     base_params(w);
     rlo::Params& P = w->P;
-    const int nl = w->nl, rb = w->rb;
     const uint32_t k = (uint32_t)cfg->k;
     // per local rank the messages it originates, in order, and their lengths (the kernel loads 64 at a time)
-    std::vector<uint32_t> own_off(nl + 1, 0);
-    for (uint32_t i = 0; i < k; i++)
-        if (cfg->origin[i] >= rb && cfg->origin[i] < rb + nl) own_off[cfg->origin[i] - rb + 1]++;
-    std::vector<int64_t> expect(nl, 0);
-    for (int lr = 0; lr < nl; lr++) {
-        expect[lr] = (int64_t)k - own_off[lr + 1];
-        own_off[lr + 1] += own_off[lr];
-    }
-    std::vector<uint32_t> own(std::max<uint32_t>(own_off[nl], 1), 0), own_len(own.size(), 0), fill(own_off.begin(), own_off.end() - 1);
-    for (uint32_t i = 0; i < k; i++)
-        if (cfg->origin[i] >= rb && cfg->origin[i] < rb + nl) {
-            const uint32_t at = fill[cfg->origin[i] - rb]++;
-            own[at] = i;
-            own_len[at] = cfg->len ? cfg->len[i] : cfg->slot;
-        }
-    if (w->d_lat_own_off.upload(own_off) || w->d_lat_own.upload(own) || w->d_send_own_len.upload(own_len) ||
-        w->d_expect_bcast.upload(expect))
+    const auto own = own_lists<uint32_t>(w, k, [&](int64_t i) { return cfg->origin[i]; });
+    std::vector<uint32_t> own_len(own.idx.size(), 0);
+    for (size_t at = 0; at < (size_t)own.off[w->nl]; at++) own_len[at] = cfg->len ? cfg->len[own.idx[at]] : cfg->slot;
+    if (w->d_lat_own_off.upload(own.off) || w->d_lat_own.upload(own.idx) || w->d_send_own_len.upload(own_len) ||
+        w->d_expect_bcast.upload(own.expect))
         return RLO_E_HIP;
-    // (MODE_LL: the hop kernel always rings the doorbells, and only that kernel runs this program)
-    P.mode = rlo::MODE_SEND | rlo::MODE_LL | (ordered ? rlo::MODE_LAT : 0u) | ((cfg->flags & RLO_FLAG_HIST) ? rlo::MODE_HIST : 0u);
+    // (MODE_LL: the hop kernel always rings the doorbells, and only that kernel runs this program; rlo_send_check
+    // refused RLO_FLAG_PROF)
+    P.mode = rlo::MODE_SEND | rlo::MODE_LL | (ordered ? rlo::MODE_LAT : 0u) | flag_modes(cfg->flags);
     P.len = cfg->slot;
     P.hop_chunks = 1u + cfg->slot / 16u;
     P.lat_own_off = w->d_lat_own_off.p;
@@ -1596,20 +1605,7 @@ int rlo_program_send(rlo_world_t* w, const rlo_send_cfg_t* cfg) {
     P.send_slot = cfg->slot;
     w->lat_rounds = 0;
     w->tl_rows = 0;
-    if (ordered) {  // the latency program's closed loop: round word, delivery counts, completion ticks
-        if (w->d_lat_count.alloc(k) || w->d_lat_out.alloc(k) || w->d_lat_round.alloc(1) || w->d_lat_obs.alloc(k)) return RLO_E_HIP;
-        P.lat_rounds = k;
-        P.lat_count = w->d_lat_count.p;
-        P.lat_out = w->d_lat_out.p;
-        P.lat_round = w->d_lat_round.p;
-        P.lat_obs = w->d_lat_obs.p;
-        if (w->L.nparts != 1) {
-            uint64_t* blk = w->pc[0] + w->L.lat_base[0];
-            P.lat_round = reinterpret_cast<uint32_t*>(blk);
-            P.lat_count = reinterpret_cast<uint32_t*>(blk + 16);
-        }
-        w->lat_rounds = k;
-    }
+    if (ordered && closed_loop(w, k)) return RLO_E_HIP;
     rc = setup_log(w, cfg->flags, cfg->log_cap, false);  // records only: dst is the payload
     if (rc) return rc;
     w->have_program = true;
@@ -1661,36 +1657,29 @@ int rlo_program_iar(rlo_world_t* w, const rlo_iar_cfg_t* cfg, int64_t nprop, con
     base_params(w);
     rlo::Params& P = w->P;
     P.own_pool = pool;
-    const int n = w->L.n, nl = w->nl, rb = w->rb;
-    std::vector<int64_t> off(nl + 1, 0), expect(nl, 0), per(n, 0);
     for (int64_t i = 0; i < nprop; i++) {
-        if (origin[i] < 0 || origin[i] >= n) return RLO_E_INVAL;
+        if (origin[i] < 0 || origin[i] >= w->L.n) return RLO_E_INVAL;
         if (16ull + data_len[i] > w->max_payload) return RLO_E_INVAL;
-        per[origin[i]]++;
-        if (origin[i] >= rb && origin[i] < rb + nl) off[origin[i] - rb + 1]++;
     }
-    for (int r = 0; r < nl; r++) off[r + 1] += off[r];
-    std::vector<int64_t> fill(off.begin(), off.end() - 1);
-    const size_t nown = (size_t)std::max<int64_t>(off[nl], 1);
-    std::vector<int32_t> ppid(nown);
-    std::vector<uint32_t> pdo(nown), pdl(nown);
+    // per local rank its proposals, in order: pid, data offset and length by place; the data in the caller's order
+    const size_t most = (size_t)std::max<int64_t>(nprop, 1);
+    std::vector<int32_t> ppid(most);
+    std::vector<uint32_t> pdo(most), pdl(most);
     std::vector<uint8_t> blob;
-    for (int64_t i = 0; i < nprop; i++) {
-        if (origin[i] < rb || origin[i] >= rb + nl) continue;
-        int64_t at = fill[origin[i] - rb]++;
+    const auto own = own_lists<int64_t>(w, nprop, [&](int64_t i) { return origin[i]; }, [&](size_t at, int64_t i) {
         ppid[at] = pid[i];
         pdo[at] = (uint32_t)blob.size();
         pdl[at] = data_len[i];
         blob.insert(blob.end(), data + data_off[i], data + data_off[i] + data_len[i]);
-    }
+    });
+    ppid.resize(own.idx.size()), pdo.resize(own.idx.size()), pdl.resize(own.idx.size());
     if (blob.empty()) blob.push_back(0);
-    for (int r = 0; r < nl; r++) expect[r] = nprop - per[rb + r];
-    if (w->d_prop_off.upload(off) || w->d_prop_pid.upload(ppid) || w->d_prop_data_off.upload(pdo) ||
-        w->d_prop_data_len.upload(pdl) || w->d_prop_data.upload(blob) || w->d_expect_dec.upload(expect))
+    if (w->d_prop_off.upload(own.off) || w->d_prop_pid.upload(ppid) || w->d_prop_data_off.upload(pdo) ||
+        w->d_prop_data_len.upload(pdl) || w->d_prop_data.upload(blob) || w->d_expect_dec.upload(own.expect))
         return RLO_E_HIP;
     uint32_t max_msg = 23;  // a decision's PBuf (:908-917); a proposal's is 16 B + its data
     for (int64_t i = 0; i < nprop; i++) max_msg = std::max<uint32_t>(max_msg, 16u + data_len[i]);
-    P.mode = rlo::MODE_IAR | ((cfg->flags & RLO_FLAG_PROF) ? rlo::MODE_PROF : 0u) | ll_mode(w, max_msg);
+    P.mode = rlo::MODE_IAR | flag_modes(cfg->flags & RLO_FLAG_PROF) | ll_mode(w, max_msg);  // (no histogram in the iar program)
     P.hop_chunks = (rlo::kHdr + max_msg + 15u) / 16u;
     {
         const int jrc = set_judge(w, cfg);
@@ -2047,41 +2036,83 @@ int rlo_reset(rlo_world_t* w, void* stream) {
     return RLO_OK;
 }
 
+// the diagnostics build's switches that are mode bits of a launch (diag_env: the product library reads none)
+static uint32_t diag_modes(uint32_t mode) {
+    static const struct { const char* env; uint32_t bit; bool nonzero; } kSwitch[] = {  // nonzero: on when set and not 0
+        {"RLO_LAZY_PUB", rlo::MODE_LAZYPUB},     // A/B: counters published after the next poll, not by the draining iteration
+        {"RLO_NO_IDLE_SPIN", rlo::MODE_NOSPIN},  // diagnostic
+        {"RLO_NO_ACQUIRE", rlo::MODE_NOACQ},     // diagnostic A/B, unsafe
+        {"RLO_NO_FAST", rlo::MODE_NOFAST},       // A/B: no lone-message fast path
+        // A/B: large-message staging rounds pipelined over two halves of stage2 (measured slower than whole rounds:
+        // 4 KiB storm 122 vs 109 ms, profiles/r2s4_pipe_ab.txt)
+        {"RLO_BIG_PIPE", rlo::MODE_PIPE, true},
+        {"RLO_HOP_PROF", rlo::MODE_HOPPROF},      // diagnostic: clocks along a doorbell hop
+        {"RLO_BULK_CORRUPT", rlo::MODE_CORRUPT},  // test: VERIFY must catch a zeroed granule
+        {"RLO_NO_HPOLLER", rlo::MODE_NOHPW},      // A/B: no wave-1 host poller
+        {"RLO_HOST_DIAG", rlo::MODE_HDIAG},       // diagnostic: command-wait counters
+    };
+    static const uint32_t on = [] {  // read once per process
+        uint32_t m = 0;
+        for (const auto& sw : kSwitch)
+            if (const char* e = diag_env(sw.env))
+                if (!sw.nonzero || std::atoi(e) != 0) m |= sw.bit;
+        return m;
+    }();
+    for (const auto& sw : kSwitch) mode &= ~sw.bit;
+    return mode | on;
+}
+
+// What a launch runs, decided once and before it has any effect (rlo_launch_ex)
+struct LaunchPlan {
+    int refuse = RLO_OK;  // RLO_E_INVAL: no kernel runs this (world, program)
+    bool hop = false;     // the hop kernel, else the progress kernel
+    int row = -1;         // the picked instantiation, a row of that kernel's table (rlo_pick_hop / rlo_pick_progress)
+    int blocks = 0;       // the grid (the one-XCD hop kernel's: per rank)
+    size_t dyn_lds = 0;   // dynamic LDS per workgroup
+};
+
 // The hop kernel (rlo_hop.hip: one wave per rank, one message at a time) runs the latency and iar programs with
 // doorbells (device judges, no host service, no bulk messages) whenever every rank-wave of the part is co-resident;
 // the diagnostics modes that instrument the progress kernel's doorbell pass (phase profile, hop profile, the no-fast-path
-// A/B) keep that kernel, and so does RLO_NO_HOP (diagnostics build: A/B of the two kernels)
-static size_t hop_lds(const rlo_world* w) {
-    // the pending-proposal table (iar only: the latency program launches without it, so more rank-waves share a CU)
-    if (!(w->P.mode & rlo::MODE_IAR)) return 0;
-    return w->P.pend_hbm ? 0 : (size_t)16u * (uint32_t)w->L.n * w->P.pend_slots;
-}
-static bool hop_eligible(rlo_world* w) {
+// A/B) keep that kernel, and so does RLO_NO_HOP (diagnostics build: A/B of the two kernels).  The send program and
+// RLO_PART_ONE_XCD worlds (every rank-wave on one XCD) run the hop kernel or nothing
+static bool plan_hop(const rlo_world* w, uint32_t mode, LaunchPlan& p) {
     const rlo::Params& P = w->P;
-    const bool send = (P.mode & rlo::MODE_SEND) != 0;  // the send program: this kernel or none (rlo_launch_ex)
-    if (!(P.mode & rlo::MODE_LL) || !(P.mode & (rlo::MODE_LAT | rlo::MODE_IAR | rlo::MODE_SEND))) return false;
-    if (P.mode & (rlo::MODE_HOST | rlo::MODE_STORM | rlo::MODE_PROF | rlo::MODE_HOPPROF | rlo::MODE_NOFAST)) return false;
-    if (send && ((P.mode & rlo::MODE_IAR) || w->d_xcd)) return false;
+    if (!(mode & rlo::MODE_LL) || !(mode & (rlo::MODE_LAT | rlo::MODE_IAR | rlo::MODE_SEND))) return false;
+    if (mode & (rlo::MODE_HOST | rlo::MODE_STORM | rlo::MODE_PROF | rlo::MODE_HOPPROF | rlo::MODE_NOFAST)) return false;
+    if ((mode & rlo::MODE_SEND) && (mode & rlo::MODE_IAR)) return false;
     // the timeline (diagnostics build) is the hop kernel's too unless RLO_TL_FULL asks for the progress kernel's
     static const bool tl_full = diag_env("RLO_TL_FULL") != nullptr;
-    if ((P.mode & rlo::MODE_TL) && tl_full) return false;
+    if ((mode & rlo::MODE_TL) && tl_full) return false;
     if (w->L.bulk_max || P.hop_chunks == 0 || P.hop_chunks > 64u) return false;
     // iar: one own proposal in flight per rank in small worlds only.  The hop kernel takes one message at a time per
     // rank; with many proposals in flight per rank (the pool, or N of them reaching every rank of a large world) the
     // progress kernel's batches win: decisions/s 4 / 8 ranks 153 K / 148 K vs 113 K / 118 K, but 64 / 256 ranks 158 K /
     // 140 K vs 254 K / 618 K and pool 16 at 8 ranks 186 K vs 686 K (profiles/r6_hop_ab.txt)
-    if ((P.mode & rlo::MODE_IAR) && (P.own_pool > 1 || w->L.n > 16)) return false;
+    if ((mode & rlo::MODE_IAR) && (P.own_pool > 1 || w->L.n > 16)) return false;
     static const bool off = diag_env("RLO_NO_HOP") != nullptr;
     if (off) return false;
-    const size_t lds = hop_lds(w);
+    // the pending-proposal table (iar only: the latency program launches without it, so more rank-waves share a CU)
+    const size_t lds = (mode & rlo::MODE_IAR) && !P.pend_hbm ? (size_t)16u * (uint32_t)w->L.n * P.pend_slots : 0;
     if (lds > 64u * 1024u) return false;
+    const int row = rlo_pick_hop(mode, P.pend_hbm != nullptr, P.sys_scope != 0, nullptr);
+    if (row < 0) return false;  // (the send program, or a system-scope world, on one XCD: no such kernel)
     int b = 0;
-    if ((send ? rlo_occupancy_hop_send(&b) : rlo_occupancy_hop(&b, lds, P.pend_hbm ? 1 : 0)) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
+    if (rlo_occupancy_hop(row, &b, lds) != hipSuccess) return (void)hipGetLastError(), false;
     // (RLO_PART_ONE_XCD: every rank-wave on the CUs of one XCD, an eighth of the GPU's)
-    return b > 0 && (int64_t)b * (w->d_xcd ? w->cus / 8 : w->cus) >= (int64_t)w->nl;
+    if (b <= 0 || (int64_t)b * (w->d_xcd ? w->cus / 8 : w->cus) < (int64_t)w->nl) return false;
+    p.hop = true, p.row = row, p.blocks = w->nl, p.dyn_lds = lds;
+    return true;
+}
+static LaunchPlan plan_launch(const rlo_world* w, uint32_t mode) {
+    if (w->d_xcd) mode |= rlo::MODE_XCD1;  // (what the launch sets: the one-XCD instantiation is the one asked)
+    LaunchPlan p;
+    if (plan_hop(w, mode, p)) return p;
+    p.row = rlo_pick_progress(w->variant, mode, w->P.pend_hbm != nullptr, nullptr);
+    p.blocks = w->nl + (w->L.bulk_max ? (int)w->nmov : 0);
+    p.dyn_lds = w->dyn_lds;
+    if ((mode & rlo::MODE_SEND) || w->d_xcd || p.row < 0) p.refuse = RLO_E_INVAL;
+    return p;
 }
 
 int rlo_launch_ex(rlo_world_t* w, void* stream, uint32_t flags) {
@@ -2090,9 +2121,11 @@ int rlo_launch_ex(rlo_world_t* w, void* stream, uint32_t flags) {
     if (!w->have_program) return RLO_E_NOPROGRAM;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(w->device));
-    // the send program runs the hop kernel or nothing, and that is settled before anything is reset or recorded (the
-    // diagnostics switches below that force the progress kernel included)
-    if ((w->P.mode & rlo::MODE_SEND) && (diag_env("RLO_NO_FAST") || diag_env("RLO_HOP_PROF") || !hop_eligible(w))) return RLO_E_INVAL;
+    // what cannot run is refused before the launch has any effect on the world
+    const uint32_t mode = diag_modes(w->P.mode);
+    const LaunchPlan plan = plan_launch(w, mode);
+    if (plan.refuse) return plan.refuse;
+    w->P.mode = mode;
     if (!(flags & RLO_LAUNCH_NO_RESET)) {
         int rc = rlo_reset(w, stream);
         if (rc) return rc;
@@ -2109,60 +2142,27 @@ int rlo_launch_ex(rlo_world_t* w, void* stream, uint32_t flags) {
     }
     if (w->P.mode & rlo::MODE_HOST) w->pk_dirty = true;  // rlo_reset clears what this launch writes
     HIPCHK(hipEventRecord(w->ev0, s));
-    // diagnostic A/B switch: publish producer counters after the next poll instead of at the end
-    // of the iteration that drained the stores
-    static const bool lazy = diag_env("RLO_LAZY_PUB") != nullptr;
-    if (lazy) w->P.mode |= rlo::MODE_LAZYPUB;
-    else w->P.mode &= ~rlo::MODE_LAZYPUB;
-    static const bool nospin = diag_env("RLO_NO_IDLE_SPIN") != nullptr;  // diagnostic
-    if (nospin) w->P.mode |= rlo::MODE_NOSPIN;
-    else w->P.mode &= ~rlo::MODE_NOSPIN;
-    static const bool noacq = diag_env("RLO_NO_ACQUIRE") != nullptr;  // diagnostic A/B, unsafe
-    if (noacq) w->P.mode |= rlo::MODE_NOACQ;
-    else w->P.mode &= ~rlo::MODE_NOACQ;
-    static const bool nofast = diag_env("RLO_NO_FAST") != nullptr;  // A/B: no lone-message fast path
-    if (nofast) w->P.mode |= rlo::MODE_NOFAST;
-    else w->P.mode &= ~rlo::MODE_NOFAST;
-    // A/B: large-message staging rounds pipelined over two halves of stage2 (measured slower than whole
-    // rounds: 4 KiB storm 122 vs 109 ms, profiles/r2s4_pipe_ab.txt)
-    static const bool pipe = [] {
-        const char* e = diag_env("RLO_BIG_PIPE");
-        return e && std::atoi(e) != 0;
-    }();
-    if (pipe) w->P.mode |= rlo::MODE_PIPE;
-    else w->P.mode &= ~rlo::MODE_PIPE;
-    static const bool hopprof = diag_env("RLO_HOP_PROF") != nullptr;  // diagnostic: clocks along a doorbell hop
-    if (hopprof) w->P.mode |= rlo::MODE_HOPPROF;
-    else w->P.mode &= ~rlo::MODE_HOPPROF;
-    static const bool corrupt = diag_env("RLO_BULK_CORRUPT") != nullptr;  // test: VERIFY must catch a zeroed granule
-    if (corrupt) w->P.mode |= rlo::MODE_CORRUPT;
-    else w->P.mode &= ~rlo::MODE_CORRUPT;
-    static const bool nohpw = diag_env("RLO_NO_HPOLLER") != nullptr;  // A/B: no wave-1 host poller
-    if (nohpw) w->P.mode |= rlo::MODE_NOHPW;
-    else w->P.mode &= ~rlo::MODE_NOHPW;
-    static const bool hdiag = diag_env("RLO_HOST_DIAG") != nullptr;  // diagnostic: command-wait counters
-    if (hdiag) w->P.mode |= rlo::MODE_HDIAG;
-    else w->P.mode &= ~rlo::MODE_HDIAG;
-    hipError_t e;
-    if (w->d_xcd) {  // RLO_PART_ONE_XCD: the hop kernel on one XCD, or nothing
-        if (!hop_eligible(w)) return RLO_E_INVAL;
+    if (w->d_xcd) {  // RLO_PART_ONE_XCD
         w->P.mode |= rlo::MODE_XCD1;
         w->P.xcd_word = w->d_xcd;  // (every program's base_params clears Params)
         HIPCHK(hipMemsetAsync(w->d_xcd, 0, 8, s));  // the placement rendezvous (rlo_hop.hip)
     }
-    if (hop_eligible(w)) {
-        w->last_hop = true;
-        e = rlo_launch_hop(&w->P, w->nl, hop_lds(w), s);
-    } else {
-        w->last_hop = false;
-        e = rlo_launch_progress(&w->P, w->nl + (w->L.bulk_max ? (int)w->nmov : 0), w->dyn_lds, s, w->variant);
-    }
+    const hipError_t e = plan.hop ? rlo_launch_hop(plan.row, &w->P, plan.blocks, plan.dyn_lds, s)
+                                  : rlo_launch_progress(plan.row, &w->P, plan.blocks, plan.dyn_lds, s);
     if (e != hipSuccess) { g_last_hip = (int)e; return RLO_E_HIP; }
     HIPCHK(hipEventRecord(w->ev1, s));
+    w->last_hop = plan.hop;
     return RLO_OK;
 }
 
 int rlo_launch(rlo_world_t* w, void* stream) { return rlo_launch_ex(w, stream, 0); }
+
+int rlo_kernel_pick(int kernel, int variant, uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]) {
+    if (!out || (kernel != 0 && kernel != 1) || (kernel == 0 && variant != 8 && variant != 4 && variant != 5)) return RLO_E_INVAL;
+    out[4] = 0;
+    const int row = kernel ? rlo_pick_hop(mode, pend_hbm, sys_scope, out) : rlo_pick_progress(variant, mode, pend_hbm, out);
+    return row < 0 ? RLO_E_INVAL : RLO_OK;
+}
 
 int rlo_stream_create(int device, void** stream) {
     if (!stream) return RLO_E_INVAL;

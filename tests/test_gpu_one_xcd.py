@@ -75,12 +75,23 @@ def test_one_xcd_iar_exact_sets(rlo, n, p, ppm):
 
 def test_one_xcd_limits(rlo):
     """Only the hop kernel's programs run in a ONE_XCD world: a storm (the progress kernel, whose rank-workgroups
-    spread over every XCD and would read the cached rings through other L2s) is refused at launch, not run; worlds
-    of more than 256 ranks, or with bulk messages, are refused at creation"""
+    spread over every XCD and would read the cached rings through other L2s) is refused at launch, not run, and
+    before the launch has any effect: the previous launch's statistics are not reset and its events not recorded
+    again; worlds of more than 256 ranks, or with bulk messages, are refused at creation"""
     with rlo.World(8, max_payload=64, one_xcd=True) as w:
+        w.program_latency(16, 64, seed=1)
+        w.run()
+        st, ms = w.stats(), w.kernel_ms()
+        assert (st["error"] == 0).all() and st["bcast_delivered"].sum() == 16 * 7 and ms > 0
         w.program_storm(64, 64, seed=3)
         with pytest.raises(Exception):
             w.run()
+        st2 = w.stats()
+        assert np.array_equal(st2["bcast_delivered"], st["bcast_delivered"])
+        assert np.array_equal(st2["bcast_sum"], st["bcast_sum"])
+        assert w.kernel_ms() == ms
+        w.wait()  # (the time between the latency launch's two events, taken again)
+        assert w.kernel_ms() == ms
         w.program_latency(16, 64, seed=1)  # the world stays usable for the programs it runs
         w.run()
         assert (w.stats()["error"] == 0).all()
