@@ -154,7 +154,9 @@ typedef struct {
     uint32_t proposal_pool, pad; /* as rlo_world_cfg_t (the same on every part)             */
 } rlo_part_cfg_t;
 int rlo_part_create(const rlo_part_cfg_t* cfg, rlo_world_t** out);
-int rlo_part_export(rlo_world_t* w, void* blob, uint32_t cap); /* returns RLO_PART_BLOB_BYTES */
+/* returns RLO_PART_BLOB_BYTES.  The blob carries a format version, which rlo_part_import / rlo_part_connect check
+ * with the rest of it: a blob of a library with another blob format is refused (RLO_E_INVAL), not misread */
+int rlo_part_export(rlo_world_t* w, void* blob, uint32_t cap);
 int rlo_part_connect(rlo_world_t* w, const void* blobs /* n_parts x RLO_PART_BLOB_BYTES, by part */, int n_parts);
 /* map part q's regions now (rlo_part_connect then skips q).  Parts in several processes import one exporter at a
  * time -- every part imports part k's regions while part k imports nothing, host barrier, next k: a part importing

@@ -9,6 +9,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cctype>
 #include <chrono>
@@ -17,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <random>
 #include <string>
 #include <thread>
@@ -129,10 +131,15 @@ uint32_t pow2_floor(uint64_t x) {
     return p;
 }
 
+// device memory its holder frees (a world's buffers go with the world)
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -328,22 +335,67 @@ int build_layout(int n, int nparts, const int32_t* pb, uint32_t max_payload, uin
     return RLO_OK;
 }
 
+// ---- a part's regions: the memory its peers map.  region_of is the one place that says what
+// a region is -- its size, where its creation nonce lives, what clears it -- and the place to add one: creation,
+// export, import, the nonce checks, reset and destruction loop over it.  The order is the nonce order (region_nonce)
+enum Region { kCtrl = 0, kVote, kHeap, kFwd, kBflag, kRegions };
+constexpr uint64_t kNonceTail = 256;  // bytes past a region that hold its creation nonce
+struct RegionDesc {
+    const char* name;
+    uint64_t bytes;         // as the layout sizes it (the blob carries it); allocated: + kNonceTail where `tail`
+    uint64_t nonce_off;     // byte offset of the creation nonce: control header word kCtrlNonceWord, which rlo_reset
+                            // keeps; the first word of the vote and heap regions, which no reset clears and only a
+                            // launch -- after every part connected -- writes; past the end of the forward rings and the
+                            // bulk flags (`tail`)
+    bool tail;
+    bool bulk_only;         // exists only in worlds with bulk messages
+    bool uncached;          // whatever the part's flags (peers and other XCDs write it)
+    uint64_t create_clear;  // bytes rlo_part_create zeroes (before it writes the nonce)
+    uint64_t reset_clear;   // bytes rlo_reset zeroes, but for a nonce word among them
+};
+RegionDesc region_of(const Layout& L, int part, int r) {
+    const uint64_t ctrl = L.ctrl_words[part] * 8, vote = L.vote_bytes[part], heap = L.heap_bytes[part],
+                   fwd = L.fwd_bytes[part], bflag = L.bflag_bytes[part];
+    constexpr uint64_t nonce_word = (uint64_t)rlo::kCtrlNonceWord * 8;
+    switch (r) {  //    name         bytes  nonce_off   tail   bulk_only uncached create_clear reset_clear
+        case kCtrl: return {"control",   ctrl,  nonce_word, false, false,    false,   ctrl,        ctrl};
+        case kVote: return {"vote",      vote,  0,          false, false,    false,   vote,        0};
+        case kHeap: return {"heap",      heap,  0,          false, true,     true,    0,           0};
+        case kFwd:  return {"forward",   fwd,   fwd,        true,  false,    false,   fwd,         fwd};
+        default:    return {"bulk-flag", bflag, bflag,      true,  true,     true,    bflag,       bflag};
+    }
+}
+bool region_exists(const Layout& L, int r) { return L.bulk_max || !region_of(L, 0, r).bulk_only; }
+
 // one part's connection record: what a peer needs to map this part's regions
 struct PartBlob {
     uint32_t magic, version;
     int32_t part, nparts, n, device;
     uint32_t cap, stride, vote_cap, pad;
     uint64_t token;  // identifies the hosting process
-    uint64_t fwd_ptr, vote_ptr, ctrl_ptr;
-    uint64_t fwd_bytes, vote_bytes, ctrl_bytes;
-    char bus[32];
-    hipIpcMemHandle_t hf, hv, hc;
-    uint64_t heap_ptr, bflag_ptr, heap_bytes, bflag_bytes;
-    hipIpcMemHandle_t hh, hb;
-    uint64_t nonce;  // written at the start of every region at creation: a peer's mapping must show it
+    char bus[32];    // PCI bus id of the part's GPU, NUL-terminated text
+    uint64_t ptr[kRegions], bytes[kRegions];  // by Region; 0 where the world has no such region
+    hipIpcMemHandle_t handle[kRegions];
+    uint64_t nonce;  // every region carries region_nonce(nonce, region) since creation: a peer's mapping must show it
 };
 static_assert(sizeof(PartBlob) <= RLO_PART_BLOB_BYTES, "blob");
+static_assert(offsetof(PartBlob, nonce) == 480, "blob: the nonce's place is part of the format");
 constexpr uint32_t kBlobMagic = 0x524C4F50u;  // "RLOP"
+constexpr uint32_t kBlobVersion = 2;          // 2: regions as arrays
+// the word region r of a part carries: different per region, so an import that maps ANOTHER region of the same part
+// fails the check too (one nonce for all five passed it)
+uint64_t region_nonce(uint64_t nonce, int r) { return nonce ^ (0x9E3779B97F4A7C15ull * (uint64_t)(r + 1)); }
+
+// the LDS layout of a part (plan_lds)
+struct LdsPlan {
+    int variant = 4;  // kernel instantiation: 8 / 4 waves, 5 = 4 waves with bulk messages
+    int waves = 4;    // rank-workgroup width: 8 (512 candidates per iteration) when each rank has a CU
+    int blocks_per_cu = 1;
+    uint32_t nsmall = 0, stage2 = 0, bpend_off = 0;
+    size_t dyn_lds = 0;
+    bool ll_ok = false;     // the doorbell instantiation of the kernel is co-resident at this world's size
+    bool pend_hbm = false;  // the pending-proposal tables in HBM, nl x N x pool x 16 B, uncached
+};
 
 uint64_t process_token() {
     static uint64_t tok = 0;
@@ -360,19 +412,24 @@ uint64_t process_token() {
 struct rlo_world {
     Layout L;
     int part = 0, nl = 0, rb = 0;  // my part, local rank count, first local rank
-    int device = 0;
+    int device = -1;  // (-1: none chosen yet)
     uint32_t max_payload = 0, flags = 0;
-    int cus = 0, blocks_per_cu = 0;
+    int cus = 0;
+    LdsPlan lds;
     bool connected = false;
     int sys_scope = 0;  // system-scope remote stores / publishes: some peer on another GPU or in another process
     uint32_t peers = 0;  // RLO_PEER_*
-    // local regions (the rings / counters this part consumes)
-    uint8_t* fwd = nullptr;
-    uint8_t* vote = nullptr;
-    uint64_t* ctrl = nullptr;
+    // this part's regions (the rings / counters it consumes; bulk worlds: its heap and flag region), by Region, and
     // every part's regions as addresses in this process
-    std::vector<uint8_t*> pf, pv;
-    std::vector<uint64_t*> pc;
+    uint8_t* reg[kRegions] = {};
+    std::vector<std::array<uint8_t*, kRegions>> peer;
+    uint8_t* fwd() const { return reg[kFwd]; }
+    uint8_t* heap() const { return reg[kHeap]; }
+    uint8_t* bflag() const { return reg[kBflag]; }
+    uint64_t* ctrl() const { return reinterpret_cast<uint64_t*>(reg[kCtrl]); }
+    uint8_t* pfwd(int q) const { return peer[q][kFwd]; }
+    uint8_t* pvote(int q) const { return peer[q][kVote]; }
+    uint64_t* pctrl(int q) const { return reinterpret_cast<uint64_t*>(peer[q][kCtrl]); }
     std::vector<void*> opened;  // hipIpc mappings to close
     std::vector<uint8_t> peer_done;  // part q's regions are mapped (rlo_part_import / rlo_part_connect)
     std::vector<rlo::RankTopo> topo;
@@ -419,33 +476,21 @@ struct rlo_world {
     uint64_t share_stage = 0;       // rlo_host_share called: rlo_program_host builds the segment
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0.f;
-    size_t dyn_lds = 0;
-    uint32_t nsmall = 8, stage2 = 1024;
-    bool ll_ok = false;  // the doorbell instantiation of the kernel is co-resident at this world's size
-    bool pend_hbm = false;  // the pending-proposal tables in HBM (plan_lds), nl x N x pool x 16 B, uncached
     uint64_t nonce = 0;     // this part's creation nonce (PartBlob.nonce)
-    uint8_t* pend_mem = nullptr;
-    int waves = 4;    // rank-workgroup width: 8 (512 candidates per iteration) when each rank has a CU
-    int variant = 4;  // kernel instantiation: 8 / 4 waves, 5 = 4 waves with bulk messages
-    // bulk messages (rlo_device.hpp): this part's heap, flag region and job rings (all uncached),
-    // every part's heap / flag region as mapped here, and the device tables the kernel indexes
-    uint8_t* heap = nullptr;
-    uint8_t* bflag = nullptr;
+    uint8_t* pend_mem = nullptr;  // the pending-proposal tables where lds.pend_hbm (pooled, uncached)
+    // bulk messages (rlo_device.hpp): this part's job rings (pooled, uncached) and the device tables the kernel indexes
     uint8_t* jmem = nullptr;
     uint64_t jmem_bytes = 0;
-    uint32_t nmov = 0, jslots = 0, bpend_off = 0;
-    std::vector<uint8_t*> ph, pbf;
+    uint32_t nmov = 0, jslots = 0;
     DevBuf<uint64_t> d_bheap, d_bflag;
     DevBuf<int32_t> d_part_of, d_part_begin;
     std::vector<uint32_t> host_bulk_q;     // host mode: next bulk sequence of each local rank
+    // closes the imports, hands the pooled regions back, frees what is not a DevBuf; the buffers then free themselves
+    ~rlo_world();
 };
 
 namespace {
 
-constexpr uint64_t kNonceTail = 256;  // bytes past a region that hold its creation nonce (rlo_part_create)
-// the word region r (0 control, 1 vote, 2 heap, 3 forward, 4 bulk flags) of a part carries: different per region, so
-// an import that maps ANOTHER region of the same part fails the check too (one nonce for all five passed it)
-uint64_t region_nonce(uint64_t nonce, int r) { return nonce ^ (0x9E3779B97F4A7C15ull * (uint64_t)(r + 1)); }
 // ---- the region pool and the import cache.  A world's regions -- the memory its peers map --
 // are never handed back to HIP: a destroyed world's regions wait here, by (device, memory type, size class), for the
 // next world of this process, and a peer's import of a region stays open here for that peer's next world.  Freeing
@@ -486,23 +531,22 @@ uint64_t pool_class(uint64_t b) {
     return (b + step - 1) / step * step;
 }
 
-int alloc_region(rlo_world* w, void** p, uint64_t bytes) {
-    const bool unc = (w->flags & RLO_PART_UNCACHED) != 0;
+int alloc_region(int device, bool unc, uint8_t** p, uint64_t bytes) {
     const uint64_t cls = pool_class(bytes ? bytes : 256);
     bool reused = false;
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         for (size_t i = 0; i < g_pool.size(); i++)
-            if (g_pool[i].device == w->device && g_pool[i].uncached == unc && g_pool[i].bytes == cls) {
-                *p = g_pool[i].p;
+            if (g_pool[i].device == device && g_pool[i].uncached == unc && g_pool[i].bytes == cls) {
+                *p = (uint8_t*)g_pool[i].p;
                 g_pool_live.push_back(g_pool[i]);
                 g_pool.erase(g_pool.begin() + (long)i);
                 reused = true;
                 break;
             }
         for (size_t i = 0; !reused && i < g_retired.size(); i++)  // a retired region is still good memory to reuse
-            if (g_retired[i].device == w->device && g_retired[i].uncached == unc && g_retired[i].bytes == cls) {
-                *p = g_retired[i].p;
+            if (g_retired[i].device == device && g_retired[i].uncached == unc && g_retired[i].bytes == cls) {
+                *p = (uint8_t*)g_retired[i].p;
                 g_pool_live.push_back(g_retired[i]);
                 g_retired.erase(g_retired.begin() + (long)i);
                 reused = true;
@@ -515,10 +559,10 @@ int alloc_region(rlo_world* w, void** p, uint64_t bytes) {
         if (e != hipSuccess) { g_last_hip = (int)e; return RLO_E_HIP; }
         return RLO_OK;
     }
-    hipError_t e = unc ? hipExtMallocWithFlags(p, cls, hipDeviceMallocUncached) : hipMalloc(p, cls);
+    hipError_t e = unc ? hipExtMallocWithFlags((void**)p, cls, hipDeviceMallocUncached) : hipMalloc((void**)p, cls);
     if (e != hipSuccess) { g_last_hip = (int)e; *p = nullptr; return RLO_E_HIP; }
     std::lock_guard<std::mutex> lk(g_pool_mu);
-    g_pool_live.push_back(PoolEnt{*p, cls, w->device, unc, false});
+    g_pool_live.push_back(PoolEnt{*p, cls, device, unc, false});
     return RLO_OK;
 }
 
@@ -637,12 +681,6 @@ JobMem job_mem(uint32_t J, uint32_t nl) {
 // pending-proposal table (N x pool x 16 B per rank, the one per-rank LDS array that grows with the WORLD
 // size) to HBM, then drops to 4 waves -- instead of silently moving every message onto the large path, as
 // the 8-GPU world (N = 2048: a 64-KiB table) did up to round 3.
-struct LdsPlan {
-    int variant = 4, waves = 4, blocks_per_cu = 1;
-    uint32_t nsmall = 0, stage2 = 0, bpend_off = 0;
-    size_t dyn_lds = 0;
-    bool ll_ok = false, pend_hbm = false;
-};
 // occupancy oracle: blocks of `variant` (| kVariantPH: its PH instantiation; ll: its doorbell form) per CU
 // at `dyn_lds` bytes of dynamic LDS
 typedef int (*OccFn)(int variant, bool ll, size_t dyn_lds);
@@ -745,20 +783,56 @@ int plan_lds(const Layout& L, int nl, int nmov, int cus, uint32_t flags, OccFn o
     return RLO_E_OCCUPANCY;
 }
 
-int size_lds(rlo_world* w) {
-    LdsPlan p;
-    const int rc = plan_lds(w->L, w->nl, (int)w->nmov, w->cus, w->flags, occ_device, &p);
-    if (rc) return rc;
-    w->variant = p.variant;
-    w->waves = p.waves;
-    w->nsmall = p.nsmall;
-    w->stage2 = p.stage2;
-    w->dyn_lds = p.dyn_lds;
-    w->bpend_off = p.bpend_off;
-    w->blocks_per_cu = p.blocks_per_cu;
-    w->ll_ok = p.ll_ok;
-    w->pend_hbm = p.pend_hbm;
+int size_lds(rlo_world* w) { return plan_lds(w->L, w->nl, (int)w->nmov, w->cus, w->flags, occ_device, &w->lds); }
+
+// ---- what rlo_part_create and rlo_layout_plan both make of a configuration, each written once.  Before the layout
+// (the pool sizes its vote rings): the slot payload, 0 = 4096, rounded up to 16-B chunks, <= 65520 (the slot header's
+// length is 16 bits, rlo_device.hpp), and the proposal pool, 0 = 2, a power of two <= kPoolMax
+int slot_config(uint32_t max_payload, uint32_t proposal_pool, uint32_t* payload, uint32_t* pend_slots) {
+    *payload = (std::max<uint32_t>(max_payload ? max_payload : 4096u, 16u) + 15u) & ~15u;
+    *pend_slots = proposal_pool ? proposal_pool : 2u;
+    if (*payload > 65520u || (*pend_slots & (*pend_slots - 1u)) || *pend_slots > (uint32_t)rlo::kPoolMax) return RLO_E_INVAL;
     return RLO_OK;
+}
+// After it (nl local ranks): the movers of a bulk world, half scatter / verify (never wait), half gather (wait only
+// for scatters).  Auto: every CU the rank-workgroups leave (>= 16): a bulk copy is HBM bound only with hundreds of
+// workgroups storing (8 ranks, 64 MiB: 12.8 GB/s algbw with 32 movers); idle movers sleep
+int mover_count(const Layout& L, uint32_t movers, int nl, int cus) {
+    if (!L.bulk_max) return 0;
+    return movers ? (int)movers : (std::max(16, cus - nl) & ~1);
+}
+// every field of rlo_world_info_t a plan gives (rlo_world_query adds what only a live world has)
+void fill_info(const Layout& L, int part, int cus, int nmov, const LdsPlan& p, rlo_world_info_t* o) {
+    std::memset(o, 0, sizeof *o);
+    o->n_ranks = L.n;
+    o->max_in_degree = L.max_in;
+    o->max_fanout = L.max_fan;
+    o->edges = (int)L.E.size();
+    o->ring_slots = L.cap;
+    o->slot_stride = L.stride;
+    o->vote_slots = L.vote_cap;
+    o->fwd_bytes = L.fwd_bytes[part];
+    o->vote_bytes = L.vote_bytes[part];
+    o->ctrl_bytes = L.ctrl_words[part] * 8;
+    o->cus = cus;
+    o->blocks_per_cu = p.blocks_per_cu;
+    o->part = part;
+    o->n_parts = L.nparts;
+    o->rank_begin = L.pb[part];
+    o->rank_end = L.pb[part + 1];
+    o->waves = p.waves;
+    o->bulk_slots = L.bslots;
+    o->movers = (uint32_t)nmov;
+    o->bulk_max = L.bulk_max;
+    o->heap_bytes = L.heap_bytes[part];
+    o->proposal_pool = L.pend_slots;
+    o->pull = L.pull && p.nsmall >= 2 ? 1u : 0u;  // as Params.pull
+    o->nsmall = p.nsmall;
+    o->stage2_bytes = p.stage2;
+    o->ll_ok = p.ll_ok ? 1u : 0u;
+    o->pend_hbm = p.pend_hbm ? 1u : 0u;
+    o->dyn_lds = (uint32_t)p.dyn_lds;
+    o->static_lds = (uint32_t)rlo_kernel_static_lds(p.variant);
 }
 
 // RankTopo of every local rank, with remote ends resolved to addresses in this process
@@ -788,24 +862,24 @@ void build_topo(rlo_world* w) {
         if (ps == w->part) {  // I produce its forward rings, consume its votes
             rlo::RankTopo& t = w->topo[ed.src - w->rb];
             for (int vc = 0; vc < 2; vc++) {
-                t.out_ring[ed.j][vc] = (uint64_t)(uintptr_t)(w->pf[pd] + L.fwd_off[e] + vc * ring_bytes);
-                t.out_tail[ed.j][vc] = (uint64_t)(uintptr_t)(w->pc[pd] + L.inbox[ed.dst] + 2 * ed.k + vc);
+                t.out_ring[ed.j][vc] = (uint64_t)(uintptr_t)(w->pfwd(pd) + L.fwd_off[e] + vc * ring_bytes);
+                t.out_tail[ed.j][vc] = (uint64_t)(uintptr_t)(w->pctrl(pd) + L.inbox[ed.dst] + 2 * ed.k + vc);
             }
             t.vin_data[ed.j] = (uint32_t)L.vote_off[e];
-            t.vin_head[ed.j] = (uint64_t)(uintptr_t)(w->pc[pd] + L.outbox[ed.dst] + 2 * L.T[ed.dst].sll + ed.k);
-            t.out_bell[ed.j] = (uint64_t)(uintptr_t)(w->pc[pd] + L.fbell[ed.dst] + (uint64_t)rlo::kBellWords * ed.k);
+            t.vin_head[ed.j] = (uint64_t)(uintptr_t)(w->pctrl(pd) + L.outbox[ed.dst] + 2 * L.T[ed.dst].sll + ed.k);
+            t.out_bell[ed.j] = (uint64_t)(uintptr_t)(w->pctrl(pd) + L.fbell[ed.dst] + (uint64_t)rlo::kBellWords * ed.k);
         }
         if (pd == w->part) {  // I consume its forward rings, produce its votes
             rlo::RankTopo& t = w->topo[ed.dst - w->rb];
             for (int vc = 0; vc < 2; vc++) {
                 t.in_data[ed.k][vc] = (uint32_t)(L.fwd_off[e] + vc * ring_bytes);
-                t.in_head[ed.k][vc] = (uint64_t)(uintptr_t)(w->pc[ps] + L.outbox[ed.src] + 2 * ed.j + vc);
+                t.in_head[ed.k][vc] = (uint64_t)(uintptr_t)(w->pctrl(ps) + L.outbox[ed.src] + 2 * ed.j + vc);
             }
             t.in_src[ed.k] = ed.src;
-            t.in_base[ed.k] = (uint64_t)(uintptr_t)w->pf[ps];  // the producer's slots (pulled payloads)
-            t.vout_ring[ed.k] = (uint64_t)(uintptr_t)(w->pv[ps] + L.vote_off[e]);
-            t.vout_tail[ed.k] = (uint64_t)(uintptr_t)(w->pc[ps] + L.inbox[ed.src] + 2 * L.in_edges[ed.src].size() + ed.j);
-            t.vout_bell[ed.k] = (uint64_t)(uintptr_t)(w->pc[ps] + L.vbell[ed.src] + 2 * ed.j);
+            t.in_base[ed.k] = (uint64_t)(uintptr_t)w->pfwd(ps);  // the producer's slots (pulled payloads)
+            t.vout_ring[ed.k] = (uint64_t)(uintptr_t)(w->pvote(ps) + L.vote_off[e]);
+            t.vout_tail[ed.k] = (uint64_t)(uintptr_t)(w->pctrl(ps) + L.inbox[ed.src] + 2 * L.in_edges[ed.src].size() + ed.j);
+            t.vout_bell[ed.k] = (uint64_t)(uintptr_t)(w->pctrl(ps) + L.vbell[ed.src] + 2 * ed.j);
         }
     }
 }
@@ -901,110 +975,83 @@ int rlo_part_create(const rlo_part_cfg_t* cfg, rlo_world_t** out) {
     if (!cfg || !out || cfg->n_parts < 1 || cfg->part < 0 || cfg->part >= cfg->n_parts) return RLO_E_INVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return RLO_E_NODEVICE;
-    rlo_world* w = new rlo_world();
-    w->max_payload = (std::max<uint32_t>(cfg->max_payload ? cfg->max_payload : 4096u, 16u) + 15u) & ~15u;
-    if (w->max_payload > 65520u) { delete w; return RLO_E_INVAL; }  // slot header: 16-bit length (rlo_device.hpp)
+    std::unique_ptr<rlo_world> owner(new rlo_world());  // every refusal below destroys what was built so far
+    rlo_world* const w = owner.get();
+    if (slot_config(cfg->max_payload, cfg->proposal_pool, &w->max_payload, &w->L.pend_slots)) return RLO_E_INVAL;
     w->flags = cfg->flags;
     // RLO_PART_ONE_XCD: one part, no bulk, <= 256 ranks (as many as one XCD's CUs hold: checked at launch), and only
     // hop-kernel programs (rlo_launch_ex)
     const bool one_xcd = (cfg->flags & RLO_PART_ONE_XCD) != 0;
-    if (one_xcd && (cfg->n_parts != 1 || cfg->bulk_max || cfg->n_ranks > 256)) { delete w; return RLO_E_INVAL; }
+    if (one_xcd && (cfg->n_parts != 1 || cfg->bulk_max || cfg->n_ranks > 256)) return RLO_E_INVAL;
     // rings and counters in uncached memory for every world, not only for parts on other GPUs: a
     // line of ring memory left in some XCD's L2 by an earlier kernel (the creation / reset fill) is
     // not invalidated by another XCD's write-through stores, and a consumer on that XCD read the
     // zeros (seen as unmarked slot headers that never became visible).  A ONE_XCD world's rings are
     // cached: every producer and consumer is on one XCD, so its L2 is the one copy.  RLO_CACHED_RINGS=1: A/B only
     if (!diag_env("RLO_CACHED_RINGS") && !one_xcd) w->flags |= RLO_PART_UNCACHED;
-    {
-        const uint32_t pp = cfg->proposal_pool ? cfg->proposal_pool : 2u;
-        if ((pp & (pp - 1u)) || pp > (uint32_t)rlo::kPoolMax) { delete w; return RLO_E_INVAL; }
-        w->L.pend_slots = pp;  // before the layout: it sizes the vote rings
-    }
     int rc = build_layout(cfg->n_ranks, cfg->n_parts, cfg->part_begin, w->max_payload, cfg->ring_slots, cfg->bulk_max,
                           cfg->bulk_slots, w->L);
-    if (rc) { delete w; return rc; }
+    if (rc) return rc;
     w->part = cfg->part;
     w->rb = w->L.pb[w->part];
     w->nl = w->L.pb[w->part + 1] - w->rb;
-    if (cfg->device >= 0 && hipSetDevice(cfg->device) != hipSuccess) { delete w; return RLO_E_HIP; }
+    if (cfg->device >= 0 && hipSetDevice(cfg->device) != hipSuccess) return RLO_E_HIP;
     (void)hipGetDevice(&w->device);
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, w->device) != hipSuccess) { delete w; return RLO_E_HIP; }
+    if (hipGetDeviceProperties(&prop, w->device) != hipSuccess) return RLO_E_HIP;
     w->cus = prop.multiProcessorCount;
     if (w->L.bulk_max) {
-        // movers: half scatter / verify (never wait), half gather (wait only for scatters).  Auto:
-        // every CU the rank-workgroups leave (>= 16): a bulk copy is HBM bound only with hundreds of
-        // workgroups storing (8 ranks, 64 MiB: 12.8 GB/s algbw with 32 movers); idle movers sleep
-        int mv = (int)cfg->movers;
-        if (mv == 0) mv = std::max(16, w->cus - w->nl) & ~1;
-        if (mv < 2) { delete w; return RLO_E_OCCUPANCY; }
+        const int mv = mover_count(w->L, cfg->movers, w->nl, w->cus);
+        if (mv < 2) return RLO_E_OCCUPANCY;
         w->nmov = (uint32_t)mv;
         // every sub-job that can be unfinished at once: per local rank B originations (SCATTER) and
         // N x B receptions (GATHER + VERIFY), each cut into min(kMaxSub, its tiles) sub-jobs (tile
         // counts grow with the length: bounded at bulk_max)
-        {
-            const uint32_t bm = (uint32_t)std::min<uint64_t>(w->L.bulk_max, 0xFFF00000ull);
-            const rlo::BulkPlan pl = rlo::bulk_plan(w->L.n, bm, true);
-            const rlo::BulkPlan p1 = rlo::bulk_plan(w->L.n, bm, false);
-            const uint64_t ts = std::max(rlo::bulk_total_tiles(pl, bm), rlo::bulk_total_tiles(p1, bm));
-            const uint64_t tg = std::max(rlo::bulk_stripe_tiles(pl, bm, 0), rlo::bulk_stripe_tiles(p1, bm, 0));
-            const uint64_t tv = (bm + rlo::kVerifyTile - 1) / rlo::kVerifyTile;
-            const uint64_t K = rlo::kMaxSub;
-            const uint64_t nl = (uint64_t)w->nl, B = w->L.bslots, N = (uint64_t)w->L.n;
-            const uint64_t need = nl * B * std::min<uint64_t>(rlo::kMaxSubScatter, ts) + nl * N * B * (std::min(K, tg) + std::min(K, tv)) + 64;
-            if (need > (1ull << 26)) { delete w; return RLO_E_INVAL; }
-            w->jslots = pow2_ceil((uint32_t)need);
-        }
+        const uint32_t bm = (uint32_t)std::min<uint64_t>(w->L.bulk_max, 0xFFF00000ull);
+        const rlo::BulkPlan pl = rlo::bulk_plan(w->L.n, bm, true);
+        const rlo::BulkPlan p1 = rlo::bulk_plan(w->L.n, bm, false);
+        const uint64_t ts = std::max(rlo::bulk_total_tiles(pl, bm), rlo::bulk_total_tiles(p1, bm));
+        const uint64_t tg = std::max(rlo::bulk_stripe_tiles(pl, bm, 0), rlo::bulk_stripe_tiles(p1, bm, 0));
+        const uint64_t tv = (bm + rlo::kVerifyTile - 1) / rlo::kVerifyTile;
+        const uint64_t K = rlo::kMaxSub;
+        const uint64_t nl = (uint64_t)w->nl, B = w->L.bslots, N = (uint64_t)w->L.n;
+        const uint64_t need = nl * B * std::min<uint64_t>(rlo::kMaxSubScatter, ts) + nl * N * B * (std::min(K, tg) + std::min(K, tv)) + 64;
+        if (need > (1ull << 26)) return RLO_E_INVAL;
+        w->jslots = pow2_ceil((uint32_t)need);
     }
     rc = size_lds(w);
-    if (rc) { delete w; return rc; }
-    const int me = w->part;
-    // (forward rings and bulk flags: + kNonceTail bytes past the region for the creation nonce, which no reset clears)
-    if (alloc_region(w, (void**)&w->fwd, w->L.fwd_bytes[me] + kNonceTail) || alloc_region(w, (void**)&w->vote, w->L.vote_bytes[me]) ||
-        alloc_region(w, (void**)&w->ctrl, w->L.ctrl_words[me] * 8)) {
-        rlo_world_destroy(w);
-        return RLO_E_HIP;
+    if (rc) return rc;
+    const bool unc = (w->flags & RLO_PART_UNCACHED) != 0;
+    for (int r = 0; r < kRegions; r++) {
+        const RegionDesc d = region_of(w->L, w->part, r);
+        if (!region_exists(w->L, r)) continue;
+        if (alloc_region(w->device, unc || d.uncached, &w->reg[r], d.bytes + (d.tail ? kNonceTail : 0))) return RLO_E_HIP;
+        if (d.create_clear) (void)hipMemset(w->reg[r], 0, d.create_clear);
     }
     if (one_xcd) {
         const hipError_t e = hipExtMallocWithFlags((void**)&w->d_xcd, 256, hipDeviceMallocUncached);
-        if (e != hipSuccess) { g_last_hip = (int)e; w->d_xcd = nullptr; rlo_world_destroy(w); return RLO_E_HIP; }
+        if (e != hipSuccess) { g_last_hip = (int)e; w->d_xcd = nullptr; return RLO_E_HIP; }
     }
-    if (w->pend_hbm) {  // uncached: a launch's workgroup may sit on another XCD than the previous launch's
-        const uint32_t keep = w->flags;
-        w->flags |= RLO_PART_UNCACHED;
-        const int e = alloc_region(w, (void**)&w->pend_mem, (uint64_t)w->nl * w->L.n * w->L.pend_slots * 16u);
-        w->flags = keep;
-        if (e) { rlo_world_destroy(w); return RLO_E_HIP; }
-    }
-    if (w->L.bulk_max) {  // heap, flags and job rings: uncached (peers and other XCDs write them)
+    // uncached: a launch's workgroup may sit on another XCD than the previous launch's
+    if (w->lds.pend_hbm && alloc_region(w->device, true, &w->pend_mem, (uint64_t)w->nl * w->L.n * w->L.pend_slots * 16u))
+        return RLO_E_HIP;
+    if (w->L.bulk_max) {  // the job rings: uncached (other XCDs write them)
         w->jmem_bytes = job_mem(w->jslots, (uint32_t)w->nl).bytes;
-        const uint32_t keep = w->flags;
-        w->flags |= RLO_PART_UNCACHED;
-        const int e = alloc_region(w, (void**)&w->heap, w->L.heap_bytes[me]) ||
-                      alloc_region(w, (void**)&w->bflag, w->L.bflag_bytes[me] + kNonceTail) || alloc_region(w, (void**)&w->jmem, w->jmem_bytes);
-        w->flags = keep;
-        if (e) { rlo_world_destroy(w); return RLO_E_HIP; }
-        (void)hipMemset(w->bflag, 0, w->L.bflag_bytes[me]);
+        if (alloc_region(w->device, true, &w->jmem, w->jmem_bytes)) return RLO_E_HIP;
         w->host_bulk_q.assign(w->nl, 0);
     }
-    (void)hipMemset(w->fwd, 0, std::max<uint64_t>(w->L.fwd_bytes[me], 1));
-    (void)hipMemset(w->vote, 0, std::max<uint64_t>(w->L.vote_bytes[me], 1));
-    (void)hipMemset(w->ctrl, 0, w->L.ctrl_words[me] * 8);
-    if (w->d_stats.alloc(w->nl)) { rlo_world_destroy(w); return RLO_E_HIP; }
-    {  // the creation nonce, in every region a peer's rlo_part_connect reads it back from through its mapping
-       // (control header word kCtrlNonceWord, which rlo_reset keeps; the first word of the vote and heap
-       // regions, which no reset clears and only a launch -- after every part connected -- writes; past the
-       // end of the forward rings and the bulk flags): a mapping that shows an earlier allocation fails the
-       // connection loudly instead of carrying messages into memory that is not this part's any more
+    if (w->d_stats.alloc(w->nl)) return RLO_E_HIP;
+    {  // the creation nonce, in every region (RegionDesc.nonce_off) a peer's rlo_part_connect reads it back from
+       // through its mapping: a mapping that shows an earlier allocation fails the connection loudly instead of
+       // carrying messages into memory that is not this part's any more
         static std::atomic<uint64_t> seq{0};
         w->nonce = splitmix64(process_token() ^ (++seq * 0x9E3779B97F4A7C15ull) ^
                               (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count());
         if (!w->nonce) w->nonce = 1;
-        void* regs[5] = {w->ctrl + rlo::kCtrlNonceWord, w->vote, w->heap, w->fwd + w->L.fwd_bytes[me],
-                         w->bflag ? w->bflag + w->L.bflag_bytes[me] : nullptr};
-        for (int i = 0; i < 5; i++) {
-            const uint64_t rn = region_nonce(w->nonce, i);
-            if (regs[i] && hipMemcpy(regs[i], &rn, 8, hipMemcpyHostToDevice) != hipSuccess) { rlo_world_destroy(w); return RLO_E_HIP; }
+        for (int r = 0; r < kRegions; r++) {
+            const uint64_t rn = region_nonce(w->nonce, r);
+            if (w->reg[r] && hipMemcpy(w->reg[r] + region_of(w->L, w->part, r).nonce_off, &rn, 8, hipMemcpyHostToDevice) != hipSuccess)
+                return RLO_E_HIP;
         }
     }
     // the null stream only: another part's persistent kernel may already run on this device
@@ -1012,7 +1059,7 @@ int rlo_part_create(const rlo_part_cfg_t* cfg, rlo_world_t** out) {
     (void)hipStreamSynchronize(nullptr);
     (void)hipEventCreate(&w->ev0);
     (void)hipEventCreate(&w->ev1);
-    *out = w;
+    *out = owner.release();
     return RLO_OK;
 }
 
@@ -1020,12 +1067,12 @@ int rlo_part_export(rlo_world_t* w, void* blob, uint32_t cap) {
     if (!w || !blob || cap < RLO_PART_BLOB_BYTES) return RLO_E_INVAL;
     if (std::getenv("RLO_DEBUG_REGIONS"))  // (which addresses a part exports, world after world)
         std::fprintf(stderr, "rlo: part %d exports ctrl %p vote %p fwd %p heap %p (%llu B) bflag %p nonce %016llx\n", w->part,
-                     (void*)w->ctrl, (void*)w->vote, (void*)w->fwd, (void*)w->heap,
-                     (unsigned long long)w->L.heap_bytes[w->part], (void*)w->bflag, (unsigned long long)w->nonce);
+                     (void*)w->reg[kCtrl], (void*)w->reg[kVote], (void*)w->reg[kFwd], (void*)w->reg[kHeap],
+                     (unsigned long long)w->L.heap_bytes[w->part], (void*)w->reg[kBflag], (unsigned long long)w->nonce);
     PartBlob b;
     std::memset(&b, 0, sizeof b);
     b.magic = kBlobMagic;
-    b.version = 1;
+    b.version = kBlobVersion;
     b.part = w->part;
     b.nparts = w->L.nparts;
     b.n = w->L.n;
@@ -1035,28 +1082,14 @@ int rlo_part_export(rlo_world_t* w, void* blob, uint32_t cap) {
     b.vote_cap = w->L.vote_cap;
     b.token = process_token();
     b.nonce = w->nonce;
-    b.fwd_ptr = (uint64_t)(uintptr_t)w->fwd;
-    b.vote_ptr = (uint64_t)(uintptr_t)w->vote;
-    b.ctrl_ptr = (uint64_t)(uintptr_t)w->ctrl;
-    b.fwd_bytes = w->L.fwd_bytes[w->part];
-    b.vote_bytes = w->L.vote_bytes[w->part];
-    b.ctrl_bytes = w->L.ctrl_words[w->part] * 8;
     HIPCHK(hipDeviceGetPCIBusId(b.bus, sizeof b.bus, w->device));
-    if (w->L.bulk_max) {
-        b.heap_ptr = (uint64_t)(uintptr_t)w->heap;
-        b.bflag_ptr = (uint64_t)(uintptr_t)w->bflag;
-        b.heap_bytes = w->L.heap_bytes[w->part];
-        b.bflag_bytes = w->L.bflag_bytes[w->part];
-    }
-    if (w->L.nparts > 1) {  // handles only where another process may map the regions (a one-part world needs none)
-        for (void* r : {(void*)w->fwd, (void*)w->vote, (void*)w->ctrl, (void*)w->heap, (void*)w->bflag})
-            if (r) mark_exported(r);
-        HIPCHK(hipIpcGetMemHandle(&b.hf, w->fwd));
-        HIPCHK(hipIpcGetMemHandle(&b.hv, w->vote));
-        HIPCHK(hipIpcGetMemHandle(&b.hc, w->ctrl));
-        if (w->L.bulk_max) {
-            HIPCHK(hipIpcGetMemHandle(&b.hh, w->heap));
-            HIPCHK(hipIpcGetMemHandle(&b.hb, w->bflag));
+    for (int r = 0; r < kRegions; r++) {
+        if (!w->reg[r]) continue;
+        b.ptr[r] = (uint64_t)(uintptr_t)w->reg[r];
+        b.bytes[r] = region_of(w->L, w->part, r).bytes;
+        if (w->L.nparts > 1) {  // handles only where another process may map the regions (a one-part world needs none)
+            mark_exported(w->reg[r]);
+            HIPCHK(hipIpcGetMemHandle(&b.handle[r], w->reg[r]));
         }
     }
     std::memset(blob, 0, RLO_PART_BLOB_BYTES);
@@ -1064,14 +1097,10 @@ int rlo_part_export(rlo_world_t* w, void* blob, uint32_t cap) {
     return (int)RLO_PART_BLOB_BYTES;
 }
 
-// the peer tables of a part (sized once per connection attempt: rlo_part_import may fill some of them first)
+// the peer table of a part (sized once per connection attempt: rlo_part_import may fill some of it first)
 static void peer_tables(rlo_world* w, int n_parts) {
-    if ((int)w->pf.size() == n_parts) return;
-    w->pf.assign(n_parts, nullptr);
-    w->pv.assign(n_parts, nullptr);
-    w->pc.assign(n_parts, nullptr);
-    w->ph.assign(n_parts, nullptr);
-    w->pbf.assign(n_parts, nullptr);
+    if ((int)w->peer.size() == n_parts) return;
+    w->peer.assign(n_parts, {});
     w->peer_done.assign(n_parts, 0);
     w->sys_scope = 0;
     w->peers = 0;
@@ -1080,16 +1109,48 @@ static void peer_tables(rlo_world* w, int n_parts) {
 // part q's blob: checked against this part's layout
 static bool blob_ok(const rlo_world* w, const PartBlob& b, int q, int n_parts) {
     const Layout& L = w->L;
-    return b.magic == kBlobMagic && b.part == q && b.nparts == n_parts && b.n == L.n && b.cap == L.cap &&
-           b.stride == L.stride && b.vote_cap == L.vote_cap && b.fwd_bytes == L.fwd_bytes[q] &&
-           b.vote_bytes == L.vote_bytes[q] && b.ctrl_bytes == L.ctrl_words[q] * 8 && b.heap_bytes == L.heap_bytes[q] &&
-           b.bflag_bytes == L.bflag_bytes[q];
+    bool ok = b.magic == kBlobMagic && b.version == kBlobVersion && b.part == q && b.nparts == n_parts && b.n == L.n &&
+              b.cap == L.cap && b.stride == L.stride && b.vote_cap == L.vote_cap;
+    for (int r = 0; r < kRegions; r++) ok = ok && b.bytes[r] == region_of(L, q, r).bytes;
+    return ok;
+}
+
+// every region of part q, as this process addresses it (w->peer[q]), must show the word its part wrote at creation.
+// b: the blob of a part in another process, whose regions are imports; nullptr: q is this part itself
+static int check_nonces(const rlo_world* w, int q, uint64_t nonce, const PartBlob* b) {
+    const Layout& L = w->L;
+    const auto word = [&](int r) { return (const void*)(w->peer[q][r] + region_of(L, q, r).nonce_off); };
+    for (int r = 0; r < kRegions; r++) {
+        if (!region_exists(L, r)) continue;
+        const RegionDesc d = region_of(L, q, r);
+        uint64_t got = 0;
+        HIPCHK(hipMemcpy(&got, word(r), 8, hipMemcpyDeviceToHost));
+        if (got == region_nonce(nonce, r)) continue;
+        if (!b) {
+            std::fprintf(stderr, "rlo: part %d: its own %s region at %p (%llu bytes) shows %016llx since creation, "
+                         "not its nonce %016llx\n", q, d.name, word(r), (unsigned long long)d.bytes, (unsigned long long)got,
+                         (unsigned long long)region_nonce(nonce, r));
+            return RLO_E_STALE;
+        }
+        // (what the mapping shows: 0 = never written, another nonce = an earlier allocation of that part)
+        std::fprintf(stderr, "rlo: part %d: the %s region of part %d (at %#llx there), as mapped here at %p, shows "
+                     "%016llx, not its nonce %016llx (its other regions' words:",
+                     w->part, d.name, q, (unsigned long long)b->ptr[r], word(r), (unsigned long long)got,
+                     (unsigned long long)region_nonce(nonce, r));
+        for (int k = 0; k < kRegions; k++) {
+            uint64_t g2 = 0;
+            if (region_exists(L, k) && hipMemcpy(&g2, word(k), 8, hipMemcpyDeviceToHost) == hipSuccess)
+                std::fprintf(stderr, " %s %016llx", region_of(L, q, k).name, (unsigned long long)g2);
+        }
+        std::fprintf(stderr, ")\n");
+        return RLO_E_STALE;
+    }
+    return RLO_OK;
 }
 
 // map part q's regions (my own: check them; same process: take the addresses; another process: hipIpc imports,
 // every one checked against the peer's creation nonce)
 static int import_peer(rlo_world* w, const PartBlob& b, int q) {
-    const Layout& L = w->L;
     char mybus[32] = {0};
     HIPCHK(hipDeviceGetPCIBusId(mybus, sizeof mybus, w->device));
     const uint64_t tok = process_token();
@@ -1103,81 +1164,30 @@ static int import_peer(rlo_world* w, const PartBlob& b, int q) {
     // parts on other GPUs store into this part's rings and heaps over xGMI: a cached part's L2
     // could hold lines those system-scope stores do not invalidate (rlo_hip.h RLO_PART_UNCACHED)
     if (w->sys_scope && !(w->flags & RLO_PART_UNCACHED)) return RLO_E_INVAL;
+    int rc = RLO_OK;
     if (q == w->part) {
-        w->pf[q] = w->fwd; w->pv[q] = w->vote; w->pc[q] = w->ctrl;
-        w->ph[q] = w->heap; w->pbf[q] = w->bflag;
         // my own regions must still show the nonce rlo_part_create wrote (memory that changes under a part
         // between its creation and its connection is not this part's to hand out)
-        const void* own[5] = {w->ctrl + rlo::kCtrlNonceWord, w->vote, L.bulk_max ? w->heap : nullptr,
-                              w->fwd + L.fwd_bytes[q], L.bulk_max ? w->bflag + L.bflag_bytes[q] : nullptr};
-        for (int i = 0; i < 5; i++) {
-            if (!own[i]) continue;
-            uint64_t got = 0;
-            HIPCHK(hipMemcpy(&got, own[i], 8, hipMemcpyDeviceToHost));
-            if (got != region_nonce(w->nonce, i)) {
-                static const char* const names[5] = {"control", "vote", "heap", "forward", "bulk-flag"};
-                std::fprintf(stderr, "rlo: part %d: its own %s region at %p (%llu bytes) shows %016llx since creation, "
-                             "not its nonce %016llx\n", q, names[i], own[i],
-                             (unsigned long long)(i == 2 ? L.heap_bytes[q] : 0), (unsigned long long)got,
-                             (unsigned long long)region_nonce(w->nonce, i));
-                return RLO_E_STALE;
-            }
-        }
+        std::copy(w->reg, w->reg + kRegions, w->peer[q].begin());
+        rc = check_nonces(w, q, w->nonce, nullptr);
     } else if (b.token == tok) {  // same process: the addresses are usable as they are
         if (b.device != w->device) {
             hipError_t e = hipDeviceEnablePeerAccess(b.device, 0);
             if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { g_last_hip = (int)e; return RLO_E_HIP; }
             (void)hipGetLastError();
         }
-        w->pf[q] = (uint8_t*)(uintptr_t)b.fwd_ptr;
-        w->pv[q] = (uint8_t*)(uintptr_t)b.vote_ptr;
-        w->pc[q] = (uint64_t*)(uintptr_t)b.ctrl_ptr;
-        w->ph[q] = (uint8_t*)(uintptr_t)b.heap_ptr;
-        w->pbf[q] = (uint8_t*)(uintptr_t)b.bflag_ptr;
+        for (int r = 0; r < kRegions; r++) w->peer[q][r] = (uint8_t*)(uintptr_t)b.ptr[r];
     } else {  // another process: map its regions (dmabuf IPC; xGMI when on another GPU)
-        void* p = nullptr;
-        HIPCHK(open_import(&p, b.hf, w->device));
-        w->opened.push_back(p);
-        w->pf[q] = (uint8_t*)p;
-        HIPCHK(open_import(&p, b.hv, w->device));
-        w->opened.push_back(p);
-        w->pv[q] = (uint8_t*)p;
-        HIPCHK(open_import(&p, b.hc, w->device));
-        w->opened.push_back(p);
-        w->pc[q] = (uint64_t*)p;
-        if (L.bulk_max) {
-            HIPCHK(open_import(&p, b.hh, w->device));
+        for (int r = 0; r < kRegions; r++) {
+            if (!region_exists(w->L, r)) continue;
+            void* p = nullptr;
+            HIPCHK(open_import(&p, b.handle[r], w->device));
             w->opened.push_back(p);
-            w->ph[q] = (uint8_t*)p;
-            HIPCHK(open_import(&p, b.hb, w->device));
-            w->opened.push_back(p);
-            w->pbf[q] = (uint8_t*)p;
+            w->peer[q][r] = (uint8_t*)p;
         }
-        // every mapped region must show the peer's creation nonce (rlo_part_create)
-        const void* regs[5] = {w->pc[q] + rlo::kCtrlNonceWord, w->pv[q], L.bulk_max ? w->ph[q] : nullptr,
-                               w->pf[q] + L.fwd_bytes[q], L.bulk_max ? w->pbf[q] + L.bflag_bytes[q] : nullptr};
-        for (int i = 0; i < 5; i++) {
-            if (!regs[i]) continue;
-            uint64_t got = 0;
-            HIPCHK(hipMemcpy(&got, regs[i], 8, hipMemcpyDeviceToHost));
-            if (got != region_nonce(b.nonce, i)) {
-                static const char* const names[5] = {"control", "vote", "heap", "forward", "bulk-flag"};
-                // (what the mapping shows: 0 = never written, another nonce = an earlier allocation of that part)
-                const uint64_t eva[5] = {b.ctrl_ptr, b.vote_ptr, b.heap_ptr, b.fwd_ptr, b.bflag_ptr};
-                std::fprintf(stderr, "rlo: part %d: the %s region of part %d (at %#llx there), as mapped here at %p, shows "
-                             "%016llx, not its nonce %016llx (its other regions' words:",
-                             w->part, names[i], q, (unsigned long long)eva[i], regs[i], (unsigned long long)got,
-                             (unsigned long long)region_nonce(b.nonce, i));
-                for (int k = 0; k < 5; k++) {
-                    uint64_t g2 = 0;
-                    if (regs[k] && hipMemcpy(&g2, regs[k], 8, hipMemcpyDeviceToHost) == hipSuccess)
-                        std::fprintf(stderr, " %s %016llx", names[k], (unsigned long long)g2);
-                }
-                std::fprintf(stderr, ")\n");
-                return RLO_E_STALE;
-            }
-        }
+        rc = check_nonces(w, q, b.nonce, &b);
     }
+    if (rc) return rc;
     w->peer_done[q] = 1;
     return RLO_OK;
 }
@@ -1211,8 +1221,8 @@ int rlo_part_connect(rlo_world_t* w, const void* blobs, int n_parts) {
     if (L.bulk_max) {  // the tables the movers and progress workgroups address the heaps with
         std::vector<uint64_t> hb(n_parts), fb(n_parts);
         for (int q = 0; q < n_parts; q++) {
-            hb[q] = (uint64_t)(uintptr_t)w->ph[q];
-            fb[q] = (uint64_t)(uintptr_t)w->pbf[q];
+            hb[q] = (uint64_t)(uintptr_t)w->peer[q][kHeap];
+            fb[q] = (uint64_t)(uintptr_t)w->peer[q][kBflag];
         }
         std::vector<int32_t> po(L.part_of.begin(), L.part_of.end()), pbv(L.pb.begin(), L.pb.end());
         if (w->d_bheap.upload(hb) || w->d_bflag.upload(fb) || w->d_part_of.upload(po) || w->d_part_begin.upload(pbv))
@@ -1312,68 +1322,34 @@ int rlo_part_close_imports(rlo_world_t* w) {
     for (void* p : w->opened) close_import(p);
     w->opened.clear();
     w->connected = false;
-    w->pf.clear();  // (a new connection maps the peers again)
+    w->peer.clear();  // (a new connection maps the peers again)
     return RLO_OK;
+}
+
+rlo_world::~rlo_world() {
+    if (device >= 0) (void)hipSetDevice(device);
+    for (void* p : opened) close_import(p);
+    for (uint8_t* r : reg) release_region(r);
+    release_region(jmem);
+    release_region(pend_mem);
+    if (d_xcd) (void)hipFree(d_xcd);
+    host_free(this);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
 }
 
 int rlo_world_destroy(rlo_world_t* w) {
     if (!w) return RLO_E_INVAL;
-    (void)hipSetDevice(w->device);
-    for (void* p : w->opened) close_import(p);
-    w->opened.clear();
-    for (void* r : {(void*)w->fwd, (void*)w->vote, (void*)w->ctrl, (void*)w->heap, (void*)w->bflag, (void*)w->jmem,
-                    (void*)w->pend_mem})
-        release_region(r);
-    w->d_bheap.release(); w->d_bflag.release(); w->d_part_of.release(); w->d_part_begin.release();
-    w->d_topo.release(); w->d_stats.release();
-    w->d_sched_off.release(); w->d_expect_bcast.release(); w->d_prop_off.release(); w->d_expect_dec.release();
-    w->d_sched_ids.release(); w->d_prop_data_off.release(); w->d_prop_data_len.release(); w->d_isp_off.release();
-    w->d_lat_count.release(); w->d_lat_round.release(); w->d_lat_origin.release(); w->d_prop_pid.release();
-    w->d_lat_out.release(); w->d_lat_own_off.release(); w->d_lat_own.release(); w->d_send_own_len.release(); w->d_mask.release(); w->d_prop_data.release(); w->d_log_payload.release();
-    w->d_isp.release(); w->d_log.release();
-    if (w->d_xcd) (void)hipFree(w->d_xcd);
-    host_free(w);
-    if (w->ev0) (void)hipEventDestroy(w->ev0);
-    if (w->ev1) (void)hipEventDestroy(w->ev1);
     delete w;
     return RLO_OK;
 }
 
 int rlo_world_query(const rlo_world_t* w, rlo_world_info_t* o) {
     if (!w || !o) return RLO_E_INVAL;
-    std::memset(o, 0, sizeof *o);
-    o->n_ranks = w->L.n;
-    o->max_in_degree = w->L.max_in;
-    o->max_fanout = w->L.max_fan;
-    o->edges = (int)w->L.E.size();
-    o->ring_slots = w->L.cap;
-    o->slot_stride = w->L.stride;
-    o->vote_slots = w->L.vote_cap;
-    o->fwd_bytes = w->L.fwd_bytes[w->part];
-    o->vote_bytes = w->L.vote_bytes[w->part];
-    o->ctrl_bytes = w->L.ctrl_words[w->part] * 8;
-    o->cus = w->cus;
-    o->blocks_per_cu = w->blocks_per_cu;
-    o->part = w->part;
-    o->n_parts = w->L.nparts;
-    o->rank_begin = w->rb;
-    o->rank_end = w->rb + w->nl;
+    fill_info(w->L, w->part, w->cus, (int)w->nmov, w->lds, o);
     o->sys_scope = w->sys_scope;
     o->peers = w->peers;
-    o->waves = w->waves;
-    o->bulk_slots = w->L.bslots;
-    o->movers = w->nmov;
-    o->bulk_max = w->L.bulk_max;
-    o->heap_bytes = w->L.heap_bytes[w->part];
-    o->proposal_pool = w->L.pend_slots;
-    o->pull = w->L.pull && w->nsmall >= 2 ? 1u : 0u;  // as Params.pull
-    o->nsmall = w->nsmall;
-    o->stage2_bytes = w->stage2;
-    o->ll_ok = w->ll_ok ? 1u : 0u;
-    o->pend_hbm = w->pend_hbm ? 1u : 0u;
-    o->dyn_lds = (uint32_t)w->dyn_lds;
     o->last_kernel = w->last_hop ? 1u : 0u;
-    o->static_lds = (uint32_t)rlo_kernel_static_lds(w->variant);
     return RLO_OK;
 }
 
@@ -1383,8 +1359,8 @@ int rlo_world_query(const rlo_world_t* w, rlo_world_info_t* o) {
 // path, so there the program's longest message (max_msg payload bytes) must take the small copy path.
 // RLO_NO_LL (diagnostics build) turns bells off
 static uint32_t ll_mode(const rlo_world* w, uint32_t max_msg) {
-    if (!w->ll_ok || diag_env("RLO_NO_LL")) return 0u;
-    if (w->variant == 8 && (rlo::kHdr + max_msg + 15u) / 16u > w->nsmall) return 0u;
+    if (!w->lds.ll_ok || diag_env("RLO_NO_LL")) return 0u;
+    if (w->lds.variant == 8 && (rlo::kHdr + max_msg + 15u) / 16u > w->lds.nsmall) return 0u;
     return rlo::MODE_LL;
 }
 
@@ -1398,23 +1374,23 @@ static void base_params(rlo_world* w) {
     P.rank_begin = w->rb;
     P.rank_end = w->rb + w->nl;
     P.topo = w->d_topo.p;
-    P.fwd_region = w->fwd;
+    P.fwd_region = w->fwd();
     P.fwd_region_bytes = (uint32_t)std::max<uint64_t>(w->L.fwd_bytes[w->part], 1);
     P.fwd_cap = w->L.cap;
     P.fwd_stride = w->L.stride;
-    P.vote_region = w->vote;
+    P.vote_region = w->reg[kVote];
     P.vote_region_bytes = (uint32_t)std::max<uint64_t>(w->L.vote_bytes[w->part], 1);
     P.vote_cap = w->L.vote_cap;
-    P.ctrl = w->ctrl;
+    P.ctrl = w->ctrl();
     P.ctrl_bytes = (uint32_t)(w->L.ctrl_words[w->part] * 8);
     P.sys_scope = (uint32_t)w->sys_scope;
     P.n_parts = (uint32_t)w->L.nparts;
-    for (int q = 0; q < w->L.nparts; q++) P.err_flag[q] = reinterpret_cast<uint32_t*>(w->pc[q]);
-    P.error_flag = reinterpret_cast<uint32_t*>(w->ctrl);
+    for (int q = 0; q < w->L.nparts; q++) P.err_flag[q] = reinterpret_cast<uint32_t*>(w->pctrl(q));
+    P.error_flag = reinterpret_cast<uint32_t*>(w->ctrl());
     P.stats = w->d_stats.p;
-    P.nsmall = w->nsmall;
+    P.nsmall = w->lds.nsmall;
     P.nout_max = 2u * (uint32_t)w->L.max_fan;
-    P.stage2_bytes = w->stage2;
+    P.stage2_bytes = w->lds.stage2;
     P.timeout_ticks = 100000000ull * 10;   // 10 s without progress on a rank
     P.deadline_ticks = 100000000ull * 120; // 120 s per launch
     P.window = 32;
@@ -1422,7 +1398,7 @@ static void base_params(rlo_world* w) {
     P.ring_cap = w->L.stride - rlo::kHdr;
     P.pend_slots = w->L.pend_slots;
     P.pend_hbm = reinterpret_cast<rlo::PendState*>(w->pend_mem);
-    P.pull = w->L.pull && w->nsmall >= 2 ? 1u : 0u;  // the reference chunk is staged as chunk 1
+    P.pull = w->L.pull && w->lds.nsmall >= 2 ? 1u : 0u;  // the reference chunk is staged as chunk 1
     P.relay_cap = w->L.relay_cap;
     P.own_pool = 1;  // one own proposal per engine (rootless_ops.c:241) unless a program asks for more
     if (w->L.bulk_max) {
@@ -1436,7 +1412,7 @@ static void base_params(rlo_world* w) {
         P.part_of = w->d_part_of.p;
         P.part_begin = w->d_part_begin.p;
         P.jslots = w->jslots;
-        P.bpend_off = w->bpend_off;
+        P.bpend_off = w->lds.bpend_off;
         P.jobs = reinterpret_cast<rlo::BulkJob*>(w->jmem + m.jobs);
         P.jctl = reinterpret_cast<uint64_t*>(w->jmem + m.jctl);
         P.jclaim = reinterpret_cast<uint64_t*>(w->jmem + m.jclaim);
@@ -1477,7 +1453,7 @@ static int closed_loop(rlo_world* w, uint32_t rounds) {
     P.lat_round = w->d_lat_round.p;
     P.lat_obs = w->d_lat_obs.p;
     if (w->L.nparts != 1) {  // sharded: the round word and counts are part 0's copy, peer-mapped (rlo_device.hpp kLatWords)
-        uint64_t* blk = w->pc[0] + w->L.lat_base[0];
+        uint64_t* blk = w->pctrl(0) + w->L.lat_base[0];
         P.lat_round = reinterpret_cast<uint32_t*>(blk);
         P.lat_count = reinterpret_cast<uint32_t*>(blk + 16);
     }
@@ -2011,15 +1987,18 @@ int rlo_reset(rlo_world_t* w, void* stream) {
         std::fill(w->cmd_tail.begin(), w->cmd_tail.end(), 0);
         std::fill(w->pk_head.begin(), w->pk_head.end(), 0);
     }
-    // every control word but the creation nonce (a peer still connecting may read it)
-    HIPCHK(hipMemsetAsync(w->ctrl, 0, rlo::kCtrlNonceWord * 8, s));
-    HIPCHK(hipMemsetAsync(w->ctrl + rlo::kCtrlHdrWords, 0, (w->L.ctrl_words[w->part] - rlo::kCtrlHdrWords) * 8, s));
-    // zeroed rings: a slot whose bytes are not visible yet reads without the header's slot mark
-    // (rlo_device.hpp) and is reloaded, in every launch, not only in a fresh world
-    HIPCHK(hipMemsetAsync(w->fwd, 0, w->L.fwd_bytes[w->part], s));
+    // what RegionDesc.reset_clear says: every control word but the creation nonce (a peer still connecting may read
+    // it); the rings, zeroed in every launch, not only in a fresh world: a slot whose bytes are not visible yet reads
+    // without the header's slot mark (rlo_device.hpp) and is reloaded; the bulk flags / release counts
+    for (int r = 0; r < kRegions; r++) {
+        const RegionDesc d = region_of(w->L, w->part, r);
+        if (!w->reg[r] || !d.reset_clear) continue;
+        const uint64_t upto = std::min(d.nonce_off, d.reset_clear);
+        if (upto) HIPCHK(hipMemsetAsync(w->reg[r], 0, upto, s));
+        if (d.reset_clear > upto + 8) HIPCHK(hipMemsetAsync(w->reg[r] + upto + 8, 0, d.reset_clear - upto - 8, s));
+    }
     HIPCHK(hipMemsetAsync(w->d_stats.p, 0, sizeof(rlo::RankStats) * w->nl, s));
-    if (w->L.bulk_max) {  // bulk flags / release counts, job rings (generation 0: a slot takes its first sub-job)
-        HIPCHK(hipMemsetAsync(w->bflag, 0, w->L.bflag_bytes[w->part], s));
+    if (w->L.bulk_max) {  // the job rings (generation 0: a slot takes its first sub-job)
         HIPCHK(hipMemsetAsync(w->jmem, 0, w->jmem_bytes, s));
         std::fill(w->host_bulk_q.begin(), w->host_bulk_q.end(), 0u);
     }
@@ -2108,9 +2087,9 @@ static LaunchPlan plan_launch(const rlo_world* w, uint32_t mode) {
     if (w->d_xcd) mode |= rlo::MODE_XCD1;  // (what the launch sets: the one-XCD instantiation is the one asked)
     LaunchPlan p;
     if (plan_hop(w, mode, p)) return p;
-    p.row = rlo_pick_progress(w->variant, mode, w->P.pend_hbm != nullptr, nullptr);
+    p.row = rlo_pick_progress(w->lds.variant, mode, w->P.pend_hbm != nullptr, nullptr);
     p.blocks = w->nl + (w->L.bulk_max ? (int)w->nmov : 0);
-    p.dyn_lds = w->dyn_lds;
+    p.dyn_lds = w->lds.dyn_lds;
     if ((mode & rlo::MODE_SEND) || w->d_xcd || p.row < 0) p.refuse = RLO_E_INVAL;
     return p;
 }
@@ -2185,7 +2164,7 @@ int rlo_wait(rlo_world_t* w) {
     HIPCHK(hipEventSynchronize(w->ev1));
     HIPCHK(hipEventElapsedTime(&w->last_ms, w->ev0, w->ev1));
     uint32_t err = 0;
-    HIPCHK(hipMemcpy(&err, w->ctrl, sizeof err, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&err, w->ctrl(), sizeof err, hipMemcpyDeviceToHost));
     return err ? RLO_E_DEVICE : RLO_OK;
 }
 
@@ -2202,7 +2181,7 @@ int rlo_device_error(rlo_world_t* w, uint32_t* code, uint32_t* aux) {
     if (!w) return RLO_E_INVAL;
     uint32_t v[2] = {0, 0};
     HIPCHK(hipSetDevice(w->device));
-    HIPCHK(hipMemcpy(v, w->ctrl, sizeof v, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(v, w->ctrl(), sizeof v, hipMemcpyDeviceToHost));
     if (code) *code = v[0];
     if (aux) *aux = v[1];
     return RLO_OK;
@@ -2298,50 +2277,17 @@ int rlo_bulk_plan(int n, uint64_t len, int cross, rlo_bulk_plan_t* out) {
 int rlo_layout_plan(const rlo_plan_cfg_t* cfg, rlo_world_info_t* o) {
     if (!cfg || !o || cfg->n_parts < 1 || cfg->part < 0 || cfg->part >= cfg->n_parts) return RLO_E_INVAL;
     Layout L;
-    const uint32_t mp = (std::max<uint32_t>(cfg->max_payload ? cfg->max_payload : 4096u, 16u) + 15u) & ~15u;
-    if (mp > 65520u) return RLO_E_INVAL;
-    const uint32_t pp = cfg->proposal_pool ? cfg->proposal_pool : 2u;
-    if ((pp & (pp - 1u)) || pp > (uint32_t)rlo::kPoolMax) return RLO_E_INVAL;
-    L.pend_slots = pp;
+    uint32_t mp = 0;
+    if (slot_config(cfg->max_payload, cfg->proposal_pool, &mp, &L.pend_slots)) return RLO_E_INVAL;
     int rc = build_layout(cfg->n_ranks, cfg->n_parts, nullptr, mp, cfg->ring_slots, cfg->bulk_max, cfg->bulk_slots, L);
     if (rc) return rc;
     const int cus = cfg->cus > 0 ? cfg->cus : 256;
     const int nl = L.pb[cfg->part + 1] - L.pb[cfg->part];
-    int nmov = 0;
-    if (L.bulk_max) nmov = cfg->movers ? (int)cfg->movers : (std::max(16, cus - nl) & ~1);
+    const int nmov = mover_count(L, cfg->movers, nl, cus);
     LdsPlan p;
     rc = plan_lds(L, nl, nmov, cus, cfg->flags, occ_model, &p);
     if (rc) return rc;
-    std::memset(o, 0, sizeof *o);
-    o->n_ranks = L.n;
-    o->max_in_degree = L.max_in;
-    o->max_fanout = L.max_fan;
-    o->edges = (int)L.E.size();
-    o->ring_slots = L.cap;
-    o->slot_stride = L.stride;
-    o->vote_slots = L.vote_cap;
-    o->fwd_bytes = L.fwd_bytes[cfg->part];
-    o->vote_bytes = L.vote_bytes[cfg->part];
-    o->ctrl_bytes = L.ctrl_words[cfg->part] * 8;
-    o->cus = cus;
-    o->blocks_per_cu = p.blocks_per_cu;
-    o->part = cfg->part;
-    o->n_parts = L.nparts;
-    o->rank_begin = L.pb[cfg->part];
-    o->rank_end = L.pb[cfg->part + 1];
-    o->waves = p.waves;
-    o->bulk_slots = L.bslots;
-    o->movers = (uint32_t)nmov;
-    o->bulk_max = L.bulk_max;
-    o->heap_bytes = L.heap_bytes[cfg->part];
-    o->proposal_pool = L.pend_slots;
-    o->pull = L.pull && p.nsmall >= 2 ? 1u : 0u;
-    o->nsmall = p.nsmall;
-    o->stage2_bytes = p.stage2;
-    o->ll_ok = p.ll_ok ? 1u : 0u;
-    o->pend_hbm = p.pend_hbm ? 1u : 0u;
-    o->dyn_lds = (uint32_t)p.dyn_lds;
-    o->static_lds = (uint32_t)rlo_kernel_static_lds(p.variant);
+    fill_info(L, cfg->part, cus, nmov, p, o);
     return RLO_OK;
 }
 
@@ -2360,13 +2306,13 @@ int rlo_host_bulk_stage(rlo_world_t* w, int rank, const void* data, uint64_t len
     const uint64_t need = (uint64_t)(q / B) * (uint64_t)(w->L.n - 1);
     // done(rank, s): every receiver released the slot's previous message (read through the BAR)
     const volatile uint64_t* done = reinterpret_cast<const volatile uint64_t*>(
-        w->bflag + ((uint64_t)w->nl * w->L.n * B + (uint64_t)lr * B + s) * rlo::kBulkLine);
+        w->bflag() + ((uint64_t)w->nl * w->L.n * B + (uint64_t)lr * B + s) * rlo::kBulkLine);
     const auto t0 = std::chrono::steady_clock::now();
     while (*done < need) {
         if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(timeout_us)) return RLO_E_AGAIN;
     }
     HIPCHK(hipSetDevice(w->device));
-    uint8_t* dst = w->heap + (((uint64_t)lr * w->L.n + (uint64_t)rank) * B + s) * w->L.bcap;
+    uint8_t* dst = w->heap() + (((uint64_t)lr * w->L.n + (uint64_t)rank) * B + s) * w->L.bcap;
     HIPCHK(hipMemcpy(dst, data, len, hipMemcpyHostToDevice));
     w->host_bulk_q[lr] = q + 1;
     *q_out = q;
@@ -2380,7 +2326,7 @@ int rlo_host_bulk_copy(rlo_world_t* w, int rank, const rlo_log_rec_t* ev, void* 
         return RLO_E_INVAL;
     const int lr = rank - w->rb;
     HIPCHK(hipSetDevice(w->device));
-    const uint8_t* src = w->heap + (((uint64_t)lr * w->L.n + (uint64_t)ev->origin) * w->L.bslots + ev->aux) * w->L.bcap;
+    const uint8_t* src = w->heap() + (((uint64_t)lr * w->L.n + (uint64_t)ev->origin) * w->L.bslots + ev->aux) * w->L.bcap;
     HIPCHK(hipMemcpy(dst, src, ev->len, hipMemcpyDeviceToHost));
     return RLO_OK;
 }
@@ -2494,7 +2440,7 @@ int rlo_host_proxy(rlo_world_t* w) {
             const uint32_t q = w->host_bulk_q[lr], s = q & (B - 1u);
             const uint64_t need = (uint64_t)(q / B) * (uint64_t)(w->L.n - 1);
             const volatile uint64_t* done = reinterpret_cast<const volatile uint64_t*>(
-                w->bflag + ((uint64_t)w->nl * w->L.n * B + (uint64_t)lr * B + s) * rlo::kBulkLine);
+                w->bflag() + ((uint64_t)w->nl * w->L.n * B + (uint64_t)lr * B + s) * rlo::kBulkLine);
             if (*done >= need) box->q = q;  // taken only by COMMIT, once the bytes are staged
             else rc = RLO_E_AGAIN;          // receivers still hold the slot's previous message
         } else if (box->op == rlo::SHM_OP_COMMIT) {
@@ -2508,7 +2454,7 @@ int rlo_host_proxy(rlo_world_t* w) {
             if (origin >= (uint32_t)w->L.n || s >= B || len > ((rlo::ShmHdr*)w->shm)->stage_bytes || off + len > w->L.bulk_max) {
                 rc = RLO_E_INVAL;
             } else {
-                uint8_t* slot = w->heap + (((uint64_t)lr * w->L.n + origin) * B + s) * w->L.bcap + off;
+                uint8_t* slot = w->heap() + (((uint64_t)lr * w->L.n + origin) * B + s) * w->L.bcap + off;
                 hipError_t e = hipSetDevice(w->device);
                 if (e == hipSuccess)
                     e = put ? hipMemcpy(slot, stage, len, hipMemcpyHostToDevice) : hipMemcpy(stage, slot, len, hipMemcpyDeviceToHost);

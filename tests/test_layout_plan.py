@@ -7,6 +7,9 @@ table now moves to HBM where it would crowd the stage out, and the staged chunk 
 below a slot's chunks.  The same function sizes every part a GPU creates (rlo_world.cpp plan_lds; there
 with the runtime's occupancy answers, tests/test_gpu_scale.py compares the two).
 """
+import json
+import os
+
 import pytest
 
 import rlo
@@ -65,6 +68,23 @@ def test_c5_bulk_worlds_plan(gpus):
     i = rlo.layout_plan(n, gpus, 0, max_payload=4096, bulk_max=1 << 20)
     assert i["waves"] == 4 and i["nsmall"] == 5 and n * i["bulk_slots"] <= 1024
     assert i["bulk_slots"] == 2
+
+
+def _recorded_plans():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "layout_plan.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("case", _recorded_plans(), ids=lambda c: "-".join("%s=%s" % kv for kv in sorted(c["args"].items())))
+def test_plans_as_recorded(case):
+    """every field of the plan, and every refusal, as the library answered before the part's regions, the plan and
+    the configuration's normalisation each came to one place (tests/golden/gen_layout_plan.py recorded them)"""
+    if "refused" in case:
+        with pytest.raises(rlo.RloError) as e:
+            rlo.layout_plan(**case["args"])
+        assert str(e.value) == case["refused"]
+    else:
+        assert rlo.layout_plan(**case["args"]) == case["plan"]
 
 
 def test_bulk_slots_auto_beyond_512_ranks():
