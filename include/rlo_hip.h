@@ -19,6 +19,8 @@
  *             decision bcast (RLO_submit_proposal :876 ... _iar_decision_handler :814)
  *   send    : rootless bcasts of caller-owned device buffers: payloads read from a source buffer in device
  *             memory, every receiver's copy written to a destination buffer in device memory (the hop kernel only)
+ *   send_bulk: the same interface for LARGE buffers, in a world with bulk messages: k closed-loop bcasts of up to
+ *             bulk_max bytes each, read from and written to caller-owned device memory by the mover workgroups
  *   host    : the host-service program under the drop-in rootless_ops.h (commands and pickups in host memory)
  */
 #ifndef RLO_HIP_H
@@ -265,6 +267,41 @@ int rlo_program_send(rlo_world_t* w, const rlo_send_cfg_t* cfg);
 /* the argument checks of rlo_program_send that need no GPU (pure host): RLO_OK or RLO_E_INVAL */
 int rlo_send_check(const rlo_send_cfg_t* cfg, int n_ranks, uint32_t max_payload);
 
+/* bulk send: rootless bcasts of LARGE caller-owned device buffers, in a world with bulk messages (bulk_max > 0).  k
+ * messages, closed loop: message i+1 originates when every rank has picked up message i (the latency program's loop;
+ * a total order).  Every message, from 1 byte up to bulk_max, is announced as a bulk message and moved by the mover
+ * workgroups with the world's plan (direct on one GPU, chunked across GPUs / RLO_PART_CHUNKED): the origin's movers
+ * read the bytes from `src` -- the origin's own heap slot is not written --, and each receiver's movers copy its
+ * complete heap copy into its place in `dst`: bytes [0, len) are the source's, [len, round16(len)) zero, every other
+ * byte of dst (the rest of the place, the gap up to `stride`, the origin's own place) is not written.  No byte
+ * crosses the host.  rlo_stats: bcast_delivered, originated, bcast_sum (the per-message checksum of the storm /
+ * latency programs' bulk deliveries), error.  rlo_latencies(): as for a bulk round of the latency program (pickup,
+ * not the end of the copy into dst).  RLO_FLAG_LOG: the bulk delivery records (origin, tree parent, id, len,
+ * checksum), no payload copies.  The engine cannot compare a delivered granule with a generator here (the latency
+ * program's RLO_DERR_BULK site 14), so a stale tile behind a complete count would show as wrong bytes, not an error.
+ * RLO_E_INVAL, before anything is uploaded or reset: a world without bulk messages, or whose bulk kernel has no
+ * doorbells (rlo_world_info_t.ll_ok == 0), and any argument outside the ranges below.  On the device a descriptor
+ * that cannot be a message of the program (id >= k, len > stride) raises RLO_DERR_BAD_SLOT before any store to dst.
+ * Worlds of several parts: each part passes its own src and dst. */
+typedef struct {
+    int64_t k;              /* messages, 1 .. 2^31-1; in a world of several parts <= 8192 (the shared round block)     */
+    const int32_t* origin;  /* host [k]: the rank that originates message i (any rank, any mix)                      */
+    const uint32_t* len;    /* host [k]: bytes of message i, 1 .. min(stride, bulk_max); NULL = every message is
+                               `stride` bytes                                                                       */
+    const void* src;        /* DEVICE, 16-B aligned: message i's bytes at src + i * stride, readable for
+                               round16(len[i]) bytes.  This part reads only the messages its own ranks originate.
+                               Must not change while the launch runs                                               */
+    void* dst;              /* DEVICE, 16-B aligned: local rank lr's copy of message i at lr * rank_stride + i * stride */
+    uint64_t stride;        /* bytes between messages: a multiple of 16, >= round16(max len), < 4 GiB                */
+    uint64_t rank_stride;   /* bytes between ranks in dst: a multiple of 16; 0 = k * stride; >= (k - 1) * stride +
+                               round16(len[k - 1])                                                                 */
+    uint32_t flags;         /* RLO_FLAG_LOG | RLO_FLAG_HIST                                                         */
+    uint32_t log_cap;
+} rlo_send_bulk_cfg_t;
+int rlo_program_send_bulk(rlo_world_t* w, const rlo_send_bulk_cfg_t* cfg);
+/* the argument checks of rlo_program_send_bulk that need no GPU (pure host): RLO_OK or RLO_E_INVAL */
+int rlo_send_bulk_check(const rlo_send_bulk_cfg_t* cfg, int n_ranks, uint64_t bulk_max);
+
 #define RLO_JUDGE_APPROVE 0u /* approve everything                                           */
 #define RLO_JUDGE_MASK 1u    /* decline iff mask[rank] != 0 (arg != NULL)                     */
 #define RLO_JUDGE_ISP 2u     /* testcases.c:18-37 is_proposal_approved_cb, per-rank string    */
@@ -395,7 +432,8 @@ int rlo_storm_lengths(uint64_t seed, uint64_t k, uint32_t len, uint32_t len_max,
  * kernel: 0 the progress kernel, 1 the hop kernel (as rlo_world_info_t.last_kernel); variant: 8 / 4 waves, 5 = 4 waves
  * with bulk messages (progress only); mode: the launch's mode bits (rlo_device.hpp Mode); pend_hbm, sys_scope: as
  * rlo_world_info_t.  out: the instantiation's template arguments -- progress {W, BULK, LL, PH, program mask}, hop
- * {PH, SYS, LOC, SEND, 0}.  RLO_E_INVAL: no such kernel (the hop kernel's send program, or system scope, on one XCD) */
+ * {PH, SYS, LOC, SEND, 0}.  RLO_E_INVAL: no such kernel (the hop kernel's send program, or system scope, on one XCD;
+ * the bulk send program -- mode MODE_SENDB | MODE_LL, no other program bit -- anywhere but variant 5 with doorbells) */
 int rlo_kernel_pick(int kernel, int variant, uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]);
 int rlo_host_bulk_stage(rlo_world_t* w, int rank, const void* data, uint64_t len, uint32_t timeout_us, uint32_t* q);
 int rlo_host_bulk_copy(rlo_world_t* w, int rank, const rlo_log_rec_t* ev, void* dst);

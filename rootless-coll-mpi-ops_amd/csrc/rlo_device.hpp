@@ -75,6 +75,8 @@ enum Mode : uint32_t {
     MODE_NOHPW = 262144u,   // diagnostics build, host mode A/B: no wave-1 host poller (wave 0 polls the host words itself)
     MODE_XCD1 = 524288u,    // RLO_PART_ONE_XCD: the hop kernel's rank-waves on one XCD, L2-kept (plain) hand-off stores
     MODE_SEND = 1048576u,   // the send program (rlo_hop.hip, the SEND instantiations only): bcasts of caller-owned device buffers
+    MODE_SENDB = 2097152u,  // the bulk send program (the progress kernel's bulk-send instantiation only): closed-loop bcasts
+                            //   of caller-owned device buffers as bulk messages; the kernel runs it with MODE_LAT set too
     MODE_CORRUPT = 65536u,  // diagnostics build, test of the VERIFY check: a direct scatter zeroes one granule of one copy
     MODE_HOST = 128u,  // host-service: originations / judge verdicts come from a host command ring,
                        //   deliveries / judge requests / results go to a host pickup ring (rootless_ops.h)
@@ -308,6 +310,9 @@ struct Params {
     uint8_t* send_dst;              // DEVICE, caller-owned: local rank lr's copy of message i at (lr * send_k + i) * send_slot
     const uint32_t* send_own_len;   // [lat_own entries] bytes of each own message
     uint32_t send_k, send_slot;     // messages; bytes per message place (a multiple of 16, <= 1008)
+    // the bulk send program (MODE_SENDB; appended likewise): message i's bytes at send_src + i * send_stride, local rank
+    // lr's copy at send_dst + lr * send_rank_stride + i * send_stride (send_slot unused)
+    uint64_t send_stride, send_rank_stride;
 };
 
 // ---- bulk messages (longer than a ring slot; SURVEY §8(f)1, BASELINE configs[2], [4]).
@@ -351,7 +356,8 @@ struct BulkJob {         // 64 B, one slot of a part's job ring: one SUB-job (co
     uint32_t ti0, parent;  // its first tile in the job; the job's first sub-job slot (VERIFY accounting)
     int32_t from;        // VERIFY: tree parent of the announcement (log)
     uint32_t logidx;     // VERIFY: log record to complete with the checksum, ~0u = none
-    uint32_t q, gen;     // bulk sequence; SCATTER source: 1 = heap slot (o, o, s) (host), 0 = generated
+    uint32_t q, gen;     // bulk sequence; SCATTER source: 1 = heap slot (o, o, s) (host), 0 = generated, 2 = the caller's
+                         // buffer (bulk send: Params.send_src; its VERIFY-kind job carries 2 too: the DELIVERY into send_dst)
     uint32_t total;      // tiles of the whole job
     uint32_t pjob;       // VERIFY: the parent sub-job's index, low 32 bits (its slot's generation)
 };

@@ -481,7 +481,12 @@ __device__ __forceinline__ u32x4 storm_granule(uint32_t origin, uint32_t bid, ui
 // of it.  A slot is freed as soon as its record is read, except a VERIFY job's first slot, whose
 // jdone / jsum accumulate the job until its last sub-job finished.  Exits once every progress
 // workgroup of the part has exited and no sub-job was posted for its ticket.
-template <int W, class SH>
+// BS: the movers of the bulk send program (MODE_SENDB), compiled into that program's instantiation only.  A SCATTER
+// reads the caller's source buffer (BulkJob.gen == 2) instead of generating into the origin's heap slot and reading
+// that back -- the origin's own slot is never written --, and the VERIFY-kind job is the DELIVERY: every granule of the
+// receiver's heap copy is tail-masked, stored into the caller's destination buffer and folded into the checksum.
+// There is no generator to compare a granule with, so site 14's stale-granule check does not exist here.
+template <int W, bool BS, class SH>
 __device__ __forceinline__ void mover_run(const Params& P, SH& SS, int tid) {
     BulkSh& S = SS.b;
     constexpr int kT = 64 * W;
@@ -567,6 +572,21 @@ __device__ __forceinline__ void mover_run(const Params& P, SH& SS, int tid) {
         const uint32_t len = jb.len, s = jb.slot;
         const int o = jb.origin;
         const int me = P.rank_begin + jb.lr;
+        if constexpr (BS) {
+            // a job that is no message of this program (the progress workgroups refuse such a descriptor before they
+            // post, ERR_BAD_SLOT): nothing of it is read from src or stored to dst
+            if (!((jb.kind == JOB_GATHER || jb.gen == 2u) && jb.bid < P.send_k && (uint64_t)len <= P.send_stride)) {
+                if (tid == 0) bulk_fault(P, 15, (jb.kind << 20) | (jb.bid & 0xfffffu));
+                return;
+            }
+        }
+        // bulk send: bytes [off, off + bytes) of message bid in the caller's source buffer (read for round16(len) bytes
+        // at the most), and of local rank lr's place for it in the caller's destination buffer, as uniform resources
+        // cut to that range like bulk_rsrc_at's
+        [[maybe_unused]] auto send_rsrc = [&](const uint8_t* base, uint64_t first, uint32_t off, uint32_t bytes) {
+            const uint64_t a = reinterpret_cast<uint64_t>(base) + first + (uint64_t)jb.bid * P.send_stride + off;
+            return mk_rsrc(reinterpret_cast<void*>(uni64(a)), (uint32_t)uni((int)bytes));
+        };
         if (tid == 0 && jb.kind == JOB_SCATTER && jb.ti0 == 0u) tl_mark(P, jb.bid, TL_CLAIMED);
         const BulkPlan pl = bulk_plan(n, len, P.bulk_cross != 0);
         if (jb.kind == JOB_SCATTER && pl.direct) {
@@ -575,8 +595,10 @@ __device__ __forceinline__ void mover_run(const Params& P, SH& SS, int tid) {
             // this mover's shard of every receiver's completion count
             const uint32_t off0 = jb.ti0 * pl.tile;
             const uint32_t ngr = (min(jb.ntiles * pl.tile, len - off0) + 15u) >> 4;
-            const __amdgpu_buffer_rsrc_t rs = bulk_rsrc_at(P, o, o, s, off0, 16u * ngr);
-            if (!jb.gen) {  // a device program's origination: its bytes into the origin's copy first (see below)
+            __amdgpu_buffer_rsrc_t rs;
+            if constexpr (BS) rs = send_rsrc(P.send_src, 0ull, off0, 16u * ngr);  // the caller's bytes, read once
+            else rs = bulk_rsrc_at(P, o, o, s, off0, 16u * ngr);
+            if (!BS && !jb.gen) {  // a device program's origination: its bytes into the origin's copy first (see below)
                 for (uint32_t g0 = 0; g0 < ngr; g0 += (uint32_t)kMoveDepth * kT) {
 #pragma unroll
                     for (int uu = 0; uu < kMoveDepth; uu++) {
@@ -634,8 +656,10 @@ __device__ __forceinline__ void mover_run(const Params& P, SH& SS, int tid) {
                 const uint32_t ngr = (tlen + 15u) >> 4;
                 if (jb.kind == JOB_SCATTER) {
                     const int owner = (o + 1 + (int)k) % n;
-                    const __amdgpu_buffer_rsrc_t rs = bulk_rsrc_at(P, o, o, s, off0, 16u * ngr);
-                    if (!jb.gen) {
+                    __amdgpu_buffer_rsrc_t rs;
+                    if constexpr (BS) rs = send_rsrc(P.send_src, 0ull, off0, 16u * ngr);
+                    else rs = bulk_rsrc_at(P, o, o, s, off0, 16u * ngr);
+                    if (!BS && !jb.gen) {
                         // a device program's origination: its bytes are first written into the origin's own
                         // heap slot (the copy an application would have staged, rlo_host_bulk_stage), then
                         // read back from there like the host's -- the scatter always moves the origin's copy.
@@ -729,7 +753,7 @@ __device__ __forceinline__ void mover_run(const Params& P, SH& SS, int tid) {
                             v[uu] = sys ? ld_sys(rs, 16u * g) : ld_sc1(rs, 16u * g);
                         }
                     };
-                    auto sum = [&](const u32x4 (&v)[kMoveDepth], uint32_t g0) {
+                    [[maybe_unused]] auto sum = [&](const u32x4 (&v)[kMoveDepth], uint32_t g0) {
 #pragma unroll
                         for (int uu = 0; uu < kMoveDepth; uu++) {
                             const uint32_t g = g0 + (uint32_t)uu * kT + (uint32_t)tid;
@@ -755,6 +779,34 @@ __device__ __forceinline__ void mover_run(const Params& P, SH& SS, int tid) {
                             }
                         }
                     };
+                    // bulk send, the delivery: the masked granule goes to this rank's place for the message in the
+                    // caller's buffer -- a plain 16-B store through a resource cut to the tile's bytes of that place,
+                    // so the hardware drops whatever lies outside it (no branch per granule, as in tile_copy) -- and
+                    // into the checksum
+                    [[maybe_unused]] auto deliver = [&](const u32x4 (&v)[kMoveDepth], uint32_t g0, __amdgpu_buffer_rsrc_t rd) {
+#pragma unroll
+                        for (int uu = 0; uu < kMoveDepth; uu++) {
+                            const uint32_t g = g0 + (uint32_t)uu * kT + (uint32_t)tid;
+                            const uint32_t off = off0 + 16u * g;
+                            const int b0 = (int)len - (int)off;
+                            const u32x4 w = {mask_bytes(v[uu].x, b0), mask_bytes(v[uu].y, b0 - 4),
+                                             mask_bytes(v[uu].z, b0 - 8), mask_bytes(v[uu].w, b0 - 12)};
+                            __builtin_amdgcn_raw_buffer_store_b128(w, rd, 16u * g, 0, 0);
+                            if (g < ngr) acc += chunk_mix(off >> 4, w);
+                        }
+                    };
+                    if constexpr (BS) {
+                        const __amdgpu_buffer_rsrc_t rd =
+                            send_rsrc(P.send_dst, (uint64_t)jb.lr * P.send_rank_stride, off0, 16u * ngr);
+                        load(va, 0u);
+                        for (uint32_t g0 = 0; g0 < ngr; g0 += 2u * step) {
+                            load(vb, g0 + step);
+                            deliver(va, g0, rd);
+                            if (g0 + step >= ngr) break;
+                            load(va, g0 + 2u * step);
+                            deliver(vb, g0 + step, rd);
+                        }
+                    } else {
                     load(va, 0u);
                     for (uint32_t g0 = 0; g0 < ngr; g0 += 2u * step) {
                         load(vb, g0 + step);
@@ -762,6 +814,7 @@ __device__ __forceinline__ void mover_run(const Params& P, SH& SS, int tid) {
                         if (g0 + step >= ngr) break;
                         load(va, g0 + 2u * step);
                         sum(vb, g0 + step);
+                    }
                     }
                 }
                 // workgroup sum of this tile -> the sub-job's sum (LDS; added to the job's once, below)
@@ -816,6 +869,8 @@ constexpr uint32_t kPmLat = ~(uint32_t)(MODE_STORM | MODE_IAR | MODE_HOST);
 constexpr uint32_t kPmIar = ~(uint32_t)(MODE_STORM | MODE_LAT | MODE_HOST);
 constexpr uint32_t kPmStorm = ~(uint32_t)(MODE_LAT | MODE_IAR | MODE_HOST);
 constexpr uint32_t kPmHost = ~(uint32_t)(MODE_STORM | MODE_LAT);  // the drop-in's host service (MODE_HOST | MODE_IAR)
+// the bulk send program (MODE_SENDB, launched with MODE_LAT: the latency program's closed loop); it has no timeline
+constexpr uint32_t kPmSendBulk = ~(uint32_t)(MODE_STORM | MODE_IAR | MODE_HOST | MODE_TL | MODE_CORRUPT);
 
 // PH: the pending-proposal tables live in HBM (Params.pend_hbm; worlds whose N x pool entries would crowd
 // the small copy path's stage out of LDS: the 8-GPU worlds), instantiated for the programs that hold
@@ -832,6 +887,10 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     // the small copy path); compiled out of the others
 #define PULL_ON (W == 4 && !BULK && P.pull != 0u)
     constexpr int kWaves = W, kBlock = 64 * W, kMaxCand = 64 * W;
+    // BS: the bulk send program's instantiation.  Every message is a bulk message whatever its length; its id and
+    // length come from the rank's own list (lat_own, send_own_len) instead of the round number and P.len
+    constexpr bool BS = BULK && PM == kPmSendBulk;
+#define LAT_IS_BULK (BS || P.len > P.ring_cap)
     constexpr uint32_t kHostBase = kMaxCand - kPass;  // host mode: command run staged at the last 64 candidates
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
     __shared__ Shared<W, BULK> S;
@@ -839,7 +898,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
         if (blockIdx.x >= P.n_local) {  // a mover workgroup of the same launch
             if (threadIdx.x == 0) S.b.mv_sum = 0;
             __syncthreads();
-            mover_run<W>(P, S, (int)threadIdx.x);
+            mover_run<W, BS>(P, S, (int)threadIdx.x);
             return;
         }
     }
@@ -877,6 +936,11 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     // room for the doorbell pass, and left the storm's speed as it was (profiles/r3_storm_ab.txt)
     int lane = tid & 63;
     uint64_t lt_mask = (1ull << lane) - 1ull;
+    // the length of my next origination of the latency loop (valid while S.lat_own_next is)
+    [[maybe_unused]] auto lat_len = [&]() -> uint32_t {
+        if constexpr (BS) return P.send_own_len[P.lat_own_off[lr] + S.lat_pos];
+        else return P.len;
+    };
     const __amdgpu_buffer_rsrc_t rf = mk_rsrc(P.fwd_region, P.fwd_region_bytes);
     const __amdgpu_buffer_rsrc_t rv = mk_rsrc(P.vote_region, P.vote_region_bytes);
     const uint32_t fcap_m = P.fwd_cap - 1, vcap_m = P.vote_cap - 1;
@@ -1395,7 +1459,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
         const uint32_t nv = (uint32_t)vp;  // votes to load from child j's vote ring (<= kLLVotes)
         // (a latency round of bulk messages is originated by the full path: its announcement, heap slot and
         // scatter job)
-        const bool lat_go = (PMODE(MODE_LAT)) && (!BULK || P.len <= P.ring_cap) && S.lat_own_next != 0xffffffffu &&
+        const bool lat_go = (PMODE(MODE_LAT)) && (!BULK || !LAT_IS_BULK) && S.lat_own_next != 0xffffffffu &&
                             rdl32(latr, 1) == S.lat_own_next;
         const bool iar_dev = (PMODE(MODE_IAR)) != 0;  // (host mode: decisions only -- its proposals are commands)
         const uint64_t nvm = __ballot(nv > 0u);
@@ -1403,7 +1467,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
         // announcement by this pass too, and its scatter posted here -- not a full iteration per round
         [[maybe_unused]] bool blat = false;
         if constexpr (BULK) {
-            blat = (PMODE(MODE_LAT)) && P.len > P.ring_cap && S.lat_own_next != 0xffffffffu &&
+            blat = (PMODE(MODE_LAT)) && LAT_IS_BULK && S.lat_own_next != 0xffffffffu &&
                    rdl32(latr, 1) == S.lat_own_next &&
                    S.b.sdone[S.b.bulk_q & (bsl - 1u)] >= (uint64_t)(S.b.bulk_q / bsl) * (uint64_t)(P.n - 1);
         }
@@ -1610,9 +1674,10 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
         if constexpr (BULK) {
             if (blat) {
                 const uint32_t q = S.b.bulk_q, id = S.lat_own_next;
+                const uint32_t mlen = BS ? (uint32_t)uni((int)lat_len()) : P.len;
                 // the announcement's payload, the descriptor {len, bulk sequence}, as chunk 1 of a K_HOST-style
                 // origination from the stage scratch (the judge copy's area: free at this point of the pass)
-                if (lane == 0) *reinterpret_cast<u32x4*>(stage + kBellJudge + 16u) = u32x4{P.len, q, 0u, 0u};
+                if (lane == 0) *reinterpret_cast<u32x4*>(stage + kBellJudge + 16u) = u32x4{mlen, q, 0u, 0u};
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (originate(K_HOST, (uint32_t)me | (TAG_BULK << 16) | (0xffu << 24), id, 16u, kBellJudge, out_head_r)) {
                     if (lane == 0) {
@@ -1622,8 +1687,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                         const uint32_t np = S.lat_pos + 1u;
                         S.lat_pos = np;
                         S.lat_own_next = np < S.lat_pos_n ? P.lat_own[P.lat_own_off[lr] + np] : 0xffffffffu;
-                        queue_job(S.b, P, JCLS_A, JOB_SCATTER, me, lr, q & (bsl - 1u), id, P.len,
-                                  bulk_total_tiles(bulk_plan(P.n, P.len, P.bulk_cross != 0), P.len), -1, ~0u, q, 0u);
+                        queue_job(S.b, P, JCLS_A, JOB_SCATTER, me, lr, q & (bsl - 1u), id, mlen,
+                                  bulk_total_tiles(bulk_plan(P.n, mlen, P.bulk_cross != 0), mlen), -1, ~0u, q, BS ? 2u : 0u);
                     }
                     flush_posts(S.b, P, lane);
                     done++;
@@ -1975,13 +2040,17 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                                 bulk_fault(P, 11, (e << 8) | (pe.pad0 & 0xffu));
                             if (host) {
                                 log_put<PM>(S, P, lr, LOG_DELIVER | (TAG_BULK << 8), o, pe.from, pe.bid, pe.len, -1, sl);
+                            } else if (BS && !(pe.bid < P.send_k && pe.len > 0u && (uint64_t)pe.len <= P.send_stride)) {
+                                // bulk send: a descriptor that is no message of this program -- refused before any
+                                // store to the caller's buffer (no delivery job is posted)
+                                set_error(S, P, ERR_BAD_SLOT, pe.bid);
                             } else {
                                 tl_mark(P, pe.bid, kTlGlobal + P.n_local + (uint32_t)lr);
                                 atomicAdd(&S.bcast_delivered, 1ull);
                                 const uint32_t li =
                                     log_put<PM>(S, P, lr, LOG_DELIVER | (TAG_BULK << 8), o, pe.from, pe.bid, pe.len, -1, 0, true);
                                 queue_job(S.b, P, JCLS_A, JOB_VERIFY, o, lr, sl, pe.bid, pe.len,
-                                         (pe.len + kVerifyTile - 1u) / kVerifyTile, pe.from, li, pe.q, 0u);
+                                         (pe.len + kVerifyTile - 1u) / kVerifyTile, pe.from, li, pe.q, BS ? 2u : 0u);
                                 if (PMODE(MODE_LAT)) {  // the last of N-1 pickups completes the round
                                     const uint32_t old =
                                         sys ? __hip_atomic_fetch_add(&P.lat_count[pe.bid], 1u, __ATOMIC_RELAXED,
@@ -2235,7 +2304,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 // my next round (prefetched) starts when the previous round completed everywhere
                 bool lat_ok = true;
                 if constexpr (BULK) {
-                    if (P.len > P.ring_cap) {
+                    if (LAT_IS_BULK) {
                         const uint32_t q = S.b.bulk_q;
                         lat_ok = S.b.sdone[q & (bsl - 1u)] >= (uint64_t)(q / bsl) * (uint64_t)(P.n - 1);
                     }
@@ -2540,8 +2609,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                     w0 = (uint32_t)me | (TAG_BCAST << 16) | (0xffu << 24);
                     w2 = P.len;
                     if constexpr (BULK) {
-                        if (P.len > P.ring_cap) {
-                            bdesc_len = P.len;
+                        if (LAT_IS_BULK) {
+                            bdesc_len = lat_len();
                             bdesc_q = S.b.bulk_q;
                             w0 = (uint32_t)me | (TAG_BULK << 16) | (0xffu << 24);
                             w2 = 16u;
@@ -2798,7 +2867,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                     }
                     queue_job(S.b, P, JCLS_A, JOB_SCATTER, me, lr, bq & (bsl - 1u), id, blen,
                              bulk_total_tiles(bulk_plan(P.n, blen, P.bulk_cross != 0), blen), -1, ~0u, bq,
-                             kind == K_HOST ? 1u : 0u);
+                             kind == K_HOST ? 1u : (BS ? 2u : 0u));
                 }
             }
             // pull worlds: a large bcast this rank sends on gets a slot of its relay ring -- the copy its
@@ -3357,8 +3426,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
 // (the product build fails otherwise).  Beside the general kernel of every <W, BULK, LL, PH> (kPmAll), the kernels of
 // the device programs the bench times are specialised by program (PM): 8 waves -- the storm (no doorbells), the
 // latency program and the iar program (doorbells; the iar one with the LDS or the HBM pending table); bulk worlds --
-// the latency program (C3) and the storm (C5); and the host service the drop-in runs (doorbells; every variant, LDS
-// or HBM tables).  PH: programs that hold proposals in a world with HBM pending tables (no bulk worlds: their N x B
+// the latency program (C3), the storm (C5) and the bulk send program (kPmSendBulk: the only kernel that runs it, and it
+// runs nothing else); and the host service the drop-in runs (doorbells; every variant, LDS or HBM tables).  PH: programs that hold proposals in a world with HBM pending tables (no bulk worlds: their N x B
 // bound keeps the table small).  (Rows in the order the device code has always been emitted in.)
 #define RLO_PROGRESS_ROWS(X)                                                                                     \
     X(8, false, true, true, kPmIar) X(8, false, true, true, kPmHost) X(8, false, true, true, kPmAll)              \
@@ -3368,6 +3437,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     X(8, false, true, false, kPmHost) X(8, false, true, false, kPmAll) X(8, false, false, false, kPmAll)          \
     X(4, true, true, false, kPmLat) X(4, true, false, false, kPmStorm) X(4, true, true, false, kPmHost)           \
     X(4, true, true, false, kPmAll) X(4, true, false, false, kPmAll)                                              \
+    X(4, true, true, false, kPmSendBulk)                                                                         \
     X(4, false, true, false, kPmHost) X(4, false, true, false, kPmAll) X(4, false, false, false, kPmAll)
 
 struct ProgressRow { int w; bool bulk, ll, ph; uint32_t pm; void (*kernel)(rlo::Params); };
@@ -3408,8 +3478,14 @@ extern "C" int rlo_pick_progress(int variant, uint32_t mode, int pend_hbm, uint3
                           : prog == rlo::MODE_IAR ? rlo::kPmIar
                           : prog == rlo::MODE_STORM ? rlo::kPmStorm
                                                     : rlo::kPmAll;
-    int row = progress_row(w, bulk, ll, ph, want);
-    if (row < 0) row = progress_row(w, bulk, ll, ph, rlo::kPmAll);
+    int row;
+    if ((mode & rlo::MODE_SENDB) && prog == 0u) {
+        // the bulk send program (the launch adds MODE_LAT for the kernel): its own instantiation or nothing
+        row = bulk && ll ? progress_row(4, true, true, false, rlo::kPmSendBulk) : -1;
+    } else {
+        row = progress_row(w, bulk, ll, ph, want);
+        if (row < 0) row = progress_row(w, bulk, ll, ph, rlo::kPmAll);
+    }
     if (row >= 0 && out) {
         const ProgressRow& r = kProgressRows[row];
         out[0] = (uint32_t)r.w, out[1] = r.bulk, out[2] = r.ll, out[3] = r.ph, out[4] = r.pm;

@@ -1588,6 +1588,64 @@ int rlo_program_send(rlo_world_t* w, const rlo_send_cfg_t* cfg) {
     return RLO_OK;
 }
 
+// the bulk send program (rlo_hip.h rlo_send_bulk_cfg_t): what can be refused without a GPU
+int rlo_send_bulk_check(const rlo_send_bulk_cfg_t* cfg, int n_ranks, uint64_t bulk_max) {
+    if (!cfg || n_ranks < 1 || bulk_max == 0 || cfg->k < 1 || cfg->k > 0x7FFFFFFFll || !cfg->origin) return RLO_E_INVAL;
+    const uint64_t stride = cfg->stride;
+    if (stride == 0 || (stride & 15u) || stride >= (1ull << 32)) return RLO_E_INVAL;
+    if (!cfg->len && stride > bulk_max) return RLO_E_INVAL;  // (every message is `stride` bytes)
+    if (!cfg->src || !cfg->dst || ((uintptr_t)cfg->src & 15u) || ((uintptr_t)cfg->dst & 15u)) return RLO_E_INVAL;
+    if (cfg->flags & ~(RLO_FLAG_LOG | RLO_FLAG_HIST)) return RLO_E_INVAL;
+    for (int64_t i = 0; i < cfg->k; i++) {
+        if (cfg->origin[i] < 0 || cfg->origin[i] >= n_ranks) return RLO_E_INVAL;
+        if (cfg->len && (cfg->len[i] == 0 || cfg->len[i] > stride || cfg->len[i] > bulk_max)) return RLO_E_INVAL;
+    }
+    if (cfg->rank_stride) {  // a rank's places must hold its last message
+        const uint64_t last = cfg->len ? ((uint64_t)cfg->len[cfg->k - 1] + 15u) & ~15ull : stride;
+        if ((cfg->rank_stride & 15u) || cfg->rank_stride < (uint64_t)(cfg->k - 1) * stride + last) return RLO_E_INVAL;
+    }
+    return RLO_OK;
+}
+
+int rlo_program_send_bulk(rlo_world_t* w, const rlo_send_bulk_cfg_t* cfg) {
+    if (!w || !cfg || !w->L.bulk_max) return RLO_E_INVAL;  // (a world without bulk messages: rlo_program_send's)
+    int rc = rlo_send_bulk_check(cfg, w->L.n, w->L.bulk_max);
+    if (rc) return rc;
+    // the round word and counts of a world of several parts are part 0's copy (rlo_device.hpp kLatWords)
+    if (w->L.nparts != 1 && cfg->k > rlo::kLatCap) return RLO_E_INVAL;
+    // one instantiation runs it, the bulk kernel with doorbells: a world whose ranks that kernel cannot hold
+    // co-resident (rlo_world_info_t.ll_ok == 0) has no bulk send
+    if (!ll_mode(w, 0) || w->d_xcd) return RLO_E_INVAL;
+    if (!w->connected) return RLO_E_NOTCONNECTED;
+    base_params(w);
+    rlo::Params& P = w->P;
+    const uint32_t k = (uint32_t)cfg->k;
+    const auto own = own_lists<uint32_t>(w, k, [&](int64_t i) { return cfg->origin[i]; });
+    std::vector<uint32_t> own_len(own.idx.size(), 0);
+    for (size_t at = 0; at < (size_t)own.off[w->nl]; at++)
+        own_len[at] = cfg->len ? cfg->len[own.idx[at]] : (uint32_t)cfg->stride;
+    if (w->d_lat_own_off.upload(own.off) || w->d_lat_own.upload(own.idx) || w->d_send_own_len.upload(own_len) ||
+        w->d_expect_bcast.upload(own.expect) || closed_loop(w, k))
+        return RLO_E_HIP;
+    // (the launch adds MODE_LAT for the kernel -- the program is the latency program's loop -- but the pick sees
+    // MODE_SENDB alone: rlo_pick_progress)
+    P.mode = rlo::MODE_SENDB | rlo::MODE_LL | flag_modes(cfg->flags);
+    P.lat_own_off = w->d_lat_own_off.p;
+    P.lat_own = w->d_lat_own.p;
+    P.send_own_len = w->d_send_own_len.p;
+    P.expect_bcast = w->d_expect_bcast.p;
+    P.send_src = static_cast<const uint8_t*>(cfg->src);
+    P.send_dst = static_cast<uint8_t*>(cfg->dst);
+    P.send_k = k;
+    P.send_stride = cfg->stride;
+    P.send_rank_stride = cfg->rank_stride ? cfg->rank_stride : (uint64_t)k * cfg->stride;
+    w->tl_rows = 0;
+    rc = setup_log(w, cfg->flags, cfg->log_cap, false);  // records only: dst is the payload
+    if (rc) return rc;
+    w->have_program = true;
+    return RLO_OK;
+}
+
 // the device judge registry (rlo_kernel.hip judge_eval) and its per-rank tables, for every world
 // rank (a part uses its own ranks' entries)
 static int set_judge(rlo_world* w, const rlo_iar_cfg_t* cfg) {
@@ -2002,7 +2060,7 @@ int rlo_reset(rlo_world_t* w, void* stream) {
         HIPCHK(hipMemsetAsync(w->jmem, 0, w->jmem_bytes, s));
         std::fill(w->host_bulk_q.begin(), w->host_bulk_q.end(), 0u);
     }
-    if (w->have_program && (w->P.mode & rlo::MODE_LAT)) {
+    if (w->have_program && (w->P.mode & (rlo::MODE_LAT | rlo::MODE_SENDB))) {
         HIPCHK(hipMemsetAsync(w->d_lat_count.p, 0, sizeof(uint32_t) * w->lat_rounds, s));
         HIPCHK(hipMemsetAsync(w->d_lat_out.p, 0, sizeof(uint64_t) * w->lat_rounds, s));
         HIPCHK(hipMemsetAsync(w->d_lat_round.p, 0, sizeof(uint32_t), s));
@@ -2126,8 +2184,12 @@ int rlo_launch_ex(rlo_world_t* w, void* stream, uint32_t flags) {
         w->P.xcd_word = w->d_xcd;  // (every program's base_params clears Params)
         HIPCHK(hipMemsetAsync(w->d_xcd, 0, 8, s));  // the placement rendezvous (rlo_hop.hip)
     }
-    const hipError_t e = plan.hop ? rlo_launch_hop(plan.row, &w->P, plan.blocks, plan.dyn_lds, s)
-                                  : rlo_launch_progress(plan.row, &w->P, plan.blocks, plan.dyn_lds, s);
+    // the bulk send program is the latency program's closed loop over the caller's buffers: its kernel runs with
+    // MODE_LAT set, the world keeps MODE_SENDB alone (what picks the kernel, rlo_pick_progress)
+    rlo::Params PK = w->P;
+    if (PK.mode & rlo::MODE_SENDB) PK.mode |= rlo::MODE_LAT;
+    const hipError_t e = plan.hop ? rlo_launch_hop(plan.row, &PK, plan.blocks, plan.dyn_lds, s)
+                                  : rlo_launch_progress(plan.row, &PK, plan.blocks, plan.dyn_lds, s);
     if (e != hipSuccess) { g_last_hip = (int)e; return RLO_E_HIP; }
     HIPCHK(hipEventRecord(w->ev1, s));
     w->last_hop = plan.hop;

@@ -11,7 +11,9 @@ A program spec is a dict: {"kind": "storm", "k", "len", "seed", "window", "log",
 rank 0's clock at each round's completion) or
 {"kind": "send", "origins", "slot", "src": the k * slot source bytes (NumPy), "lens", "ordered", "log", "fill"}: each
 part creates its own device buffers (dst pre-filled with `fill`, 0xA5), and st["dst"] is the world's destination
-bytes as a NumPy array [rank][message][slot].
+bytes as a NumPy array [rank][message][slot]; or
+{"kind": "send_bulk", "origins", "stride", "src": the source bytes (NumPy, message i at i * stride), "lens", "log",
+"fill"} (worlds with bulk messages): likewise, st["dst"] [rank][message][stride].
 """
 import ctypes
 import multiprocessing as mp
@@ -22,6 +24,60 @@ import numpy as np
 
 def even_bounds(n, parts):
     return [n * p // parts for p in range(parts + 1)]
+
+
+def _hip():
+    """the HIP runtime the engine's library is linked to, which its load brought in (no second copy is loaded)"""
+    from . import _lib as L
+
+    L.load()
+    for name in ("libamdhip64.so.7", "libamdhip64.so.6", "libamdhip64.so"):
+        try:
+            return ctypes.CDLL(name, mode=os.RTLD_NOLOAD)
+        except OSError:
+            continue
+    raise ImportError("the HIP runtime of librlo_hip.so is not loaded")
+
+
+class _HipBuf:
+    """a device buffer of a part: `init` a NumPy byte array (uploaded) or a byte count (filled with `fill`)"""
+
+    def __init__(self, device, init, fill=0):
+        self.hip = _hip()
+        self.device = device
+        self.nbytes = int(init.nbytes if isinstance(init, np.ndarray) else init)
+        self.p = ctypes.c_void_p()
+        self._set_device()
+        self._chk(self.hip.hipMalloc(ctypes.byref(self.p), ctypes.c_size_t(max(self.nbytes, 16))), "hipMalloc")
+        if isinstance(init, np.ndarray):
+            self._chk(self.hip.hipMemcpy(self.p, ctypes.c_void_p(init.ctypes.data), ctypes.c_size_t(self.nbytes), 1), "hipMemcpy")
+        else:
+            self._chk(self.hip.hipMemset(self.p, ctypes.c_int(fill), ctypes.c_size_t(self.nbytes)), "hipMemset")
+        self._chk(self.hip.hipDeviceSynchronize(), "hipDeviceSynchronize")
+
+    def _set_device(self):
+        if self.device >= 0:
+            self._chk(self.hip.hipSetDevice(self.device), "hipSetDevice")
+
+    @staticmethod
+    def _chk(rc, what):
+        if rc:
+            raise RuntimeError("%s failed: hipError %d" % (what, rc))
+
+    def extent(self):
+        return (self.p.value, self.nbytes)
+
+    def download(self):
+        out = np.empty(self.nbytes, dtype=np.uint8)
+        self._set_device()
+        self._chk(self.hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), self.p, ctypes.c_size_t(self.nbytes), 2), "hipMemcpy")
+        return out
+
+    def free(self):
+        if self.p:
+            self._set_device()
+            self.hip.hipFree(self.p)
+            self.p = ctypes.c_void_p()
 
 
 def _program(w, spec):
@@ -49,19 +105,32 @@ def _program(w, spec):
         w._send_bufs = (src, dst)
         w.program_send(spec["origins"], src, dst, slot, lens=spec.get("lens"), ordered=spec.get("ordered", False),
                        log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False))
+    elif spec["kind"] == "send_bulk":
+        # the part's own device buffers, as for "send", but allocated through the HIP runtime the engine itself uses: a
+        # spawned part process has no other (torch found no GPU there once the engine's runtime was up)
+        k, stride = len(spec["origins"]), spec["stride"]
+        src = _HipBuf(w.device, np.ascontiguousarray(spec["src"], dtype=np.uint8).reshape(-1))
+        dst = _HipBuf(w.device, w.n_local * k * stride, fill=spec.get("fill", 0xA5))
+        w._send_bufs = (src, dst)
+        w.program_send_bulk(spec["origins"], src.extent(), dst.extent(), stride, lens=spec.get("lens"),
+                            log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False))
     else:
         raise ValueError(spec["kind"])
 
 
 def _collect(w, spec):
     st = w.stats()
-    if spec["kind"] == "send":
+    if spec["kind"] in ("send", "send_bulk"):
         w.info_now()  # (last_kernel: the kernel this launch ran)
     out = {"rank_begin": w.rank_begin, "stats": st, "ms": w.kernel_ms(), "info": dict(w.info)}
     if spec["kind"] == "lat" and w.rank_begin == 0:
         out["rounds"] = w.round_ticks()
     if spec["kind"] == "send":  # this part's destination buffer: [local rank][message][slot] bytes
         out["dst"] = w._send_bufs[1].cpu().numpy().reshape(w.n_local, len(spec["origins"]), spec["slot"])
+    if spec["kind"] == "send_bulk":
+        out["dst"] = w._send_bufs[1].download().reshape(w.n_local, len(spec["origins"]), spec["stride"])
+        for b in w._send_bufs:
+            b.free()
     if spec.get("log"):
         cap = spec.get("log_cap", 0) or 1024
         out["logs"] = {r: w.log(r, cap=cap, payload=spec["kind"] == "storm") for r in range(w.rank_begin, w.rank_end)}

@@ -10,6 +10,9 @@ Programs map the reference's application loops onto the device:
   iar()      -- RLO_submit_proposal / vote / decision (rootless_ops.c:668-917)
   send()     -- bcasts of the caller's own device buffers, device memory to device memory (program_send,
                 bcast_tensor; the hop kernel only)
+  send_bulk() -- the same for large buffers in a world with bulk messages: closed-loop bulk bcasts read from and
+                written to the caller's device buffers by the mover workgroups (program_send_bulk; bcast_tensor of a
+                bulk world)
 """
 import ctypes
 
@@ -212,10 +215,68 @@ class World:
         check(self.lib.rlo_program_send(self.h, ctypes.byref(cfg)), "rlo_program_send")
         self._lat_rounds = k if ordered else 0
 
+    def program_send_bulk(self, origins, src, dst, stride, lens=None, rank_stride=0, log=False, hist=False, log_cap=0):
+        """rlo_program_send_bulk (worlds with bulk messages): message i (len(origins) of them, closed loop) is a bulk
+        bcast from rank origins[i] of the lens[i] (None: stride) bytes at src + i * stride, DEVICE memory; local rank
+        lr's copy lands at dst + lr * rank_stride + i * stride (rank_stride 0: k * stride), DEVICE memory.  src / dst
+        as for program_send, 16-B aligned; src is read for round16(lens[i]) bytes of each message.  latencies_ticks()
+        as for a bulk round of the latency program."""
+        origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
+        k = int(origin.size)
+        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
+        if ln is not None and ln.size != k:
+            raise ValueError("program_send_bulk: %d lengths for %d messages" % (ln.size, k))
+        sp, sn = _dev_extent(src)
+        dp, dn = _dev_extent(dst)
+        if k and stride > 0 and stride % 16 == 0 and rank_stride % 16 == 0:
+            # the buffers hold what the program reads and writes (the argument ranges themselves: rlo_send_bulk_check)
+            last = -(-int(ln[-1] if ln is not None else stride) // 16) * 16
+            rs = rank_stride or k * stride
+            if sn < (k - 1) * stride + last or dn < (self.n_local - 1) * rs + (k - 1) * stride + last:
+                raise ValueError("program_send_bulk: src holds %d bytes, dst %d: too small for %d messages of stride %d"
+                                 % (sn, dn, k, stride))
+        cfg = L.SendBulkCfg()
+        cfg.k = k
+        cfg.origin = origin.ctypes.data
+        cfg.len = None if ln is None else ln.ctypes.data
+        cfg.src, cfg.dst = sp, dp
+        cfg.stride, cfg.rank_stride = stride, rank_stride
+        cfg.flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0)
+        cfg.log_cap = log_cap
+        self._keep = [origin, ln, src, dst, cfg]
+        check(self.lib.rlo_program_send_bulk(self.h, ctypes.byref(cfg)), "rlo_program_send_bulk")
+        self._lat_rounds = k
+
+    def _bcast_tensor_bulk(self, origin, t, stream):
+        """bcast_tensor in a world with bulk messages: the bulk send program, fragments of at most bulk_max"""
+        import torch
+
+        n, nbytes = self.n, t.numel() * t.element_size()
+        frags = bulk_fragments(nbytes, self.info["bulk_max"])
+        k, stride = len(frags), frags[0][1] + (-frags[0][1]) % 16
+        row = nbytes + (-nbytes) % 16
+        flat = t.reshape(-1).view(torch.uint8)
+        if nbytes % 16 == 0 and flat.data_ptr() % 16 == 0:
+            src = flat
+        else:  # a padded staging copy: t is never read past its end
+            src = torch.empty(row, dtype=torch.uint8, device=t.device)
+            src[:nbytes].copy_(flat)
+        dst = torch.empty((n, row), dtype=torch.uint8, device=t.device)
+        self.program_send_bulk([origin] * k, src, dst, stride, lens=[f[1] for f in frags], rank_stride=row)
+        if stream is None:
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+        self.launch(stream=stream)
+        self.wait()
+        out = dst[:, :nbytes].contiguous().view(t.dtype).reshape((n,) + tuple(t.shape))
+        out[origin].copy_(t)
+        return out
+
     def bcast_tensor(self, origin, t, stream=None):
-        """Broadcast the contiguous CUDA tensor t (any dtype, any size) from rank `origin` of a one-part world through
-        the send program, in messages of at most 1008 bytes, on torch's current stream (or `stream`, a raw
-        hipStream_t): a kernel that produced t on that stream just before needs no synchronise.  Returns a tensor of
+        """Broadcast the contiguous CUDA tensor t (any dtype, any size) from rank `origin` of a one-part world, on
+        torch's current stream (or `stream`, a raw hipStream_t): a kernel that produced t on that stream just before
+        needs no synchronise.  A world without bulk messages sends it through the send program in messages of at most
+        1008 bytes; a world with bulk messages through the bulk send program in messages of at most bulk_max bytes
+        (bulk_fragments), moved at the bulk path's bandwidth.  Returns a tensor of
         shape [n, *t.shape] and t's dtype: row r is rank r's copy (the origin's row is t itself, copied here)."""
         import torch
 
@@ -228,6 +289,8 @@ class World:
         n, nbytes = self.n, t.numel() * t.element_size()
         if nbytes == 0:
             return t.unsqueeze(0).repeat((n,) + (1,) * t.dim())
+        if self.info["bulk_max"]:
+            return self._bcast_tensor_bulk(origin, t, stream)
         slot = min(1008, self.info["slot_stride"] - 16)
         frags = send_fragments(nbytes, slot)
         k = len(frags)
@@ -347,6 +410,33 @@ def send_fragments(nbytes, slot=1008):
     if slot <= 0 or slot % 16 or slot > 1008:
         raise ValueError("send_fragments: slot must be a multiple of 16 in 16 .. 1008")
     return [(off, min(slot, nbytes - off)) for off in range(0, max(int(nbytes), 0), slot)]
+
+
+def bulk_fragments(nbytes, bulk_max):
+    """the (offset, len) fragments that cover nbytes as bulk messages of a world with this bulk_max, in order: each at
+    most bulk_max rounded down to 16 bytes, every one but the last that long (a multiple of 16, so every fragment
+    starts 16-B aligned): the messages World.bcast_tensor sends in a bulk world.  Pure Python, no GPU"""
+    frag = int(bulk_max) // 16 * 16
+    if frag <= 0:
+        raise ValueError("bulk_fragments: bulk_max must be at least 16")
+    return [(off, min(frag, nbytes - off)) for off in range(0, max(int(nbytes), 0), frag)]
+
+
+def send_bulk_check(origins, stride, n_ranks, bulk_max, lens=None, rank_stride=0, src=0x1000, dst=0x1000, flags=0):
+    """rlo_send_bulk_check: the argument checks of the bulk send program that need no GPU; returns RLO_OK or
+    RLO_E_INVAL (src / dst: pointers as integers, never dereferenced)"""
+    origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
+    ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
+    if ln is not None and ln.size != origin.size:
+        raise ValueError("send_bulk_check: %d lengths for %d messages" % (ln.size, origin.size))
+    cfg = L.SendBulkCfg()
+    cfg.k = int(origin.size)
+    cfg.origin = origin.ctypes.data if origin.size else None
+    cfg.len = None if ln is None or not ln.size else ln.ctypes.data
+    cfg.src, cfg.dst = src, dst
+    cfg.stride, cfg.rank_stride = stride, rank_stride
+    cfg.flags = flags
+    return L.load().rlo_send_bulk_check(ctypes.byref(cfg), n_ranks, bulk_max)
 
 
 def pool_trim(what):
