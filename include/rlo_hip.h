@@ -435,6 +435,11 @@ int rlo_storm_lengths(uint64_t seed, uint64_t k, uint32_t len, uint32_t len_max,
  * {PH, SYS, LOC, SEND, 0}.  RLO_E_INVAL: no such kernel (the hop kernel's send program, or system scope, on one XCD;
  * the bulk send program -- mode MODE_SENDB | MODE_LL, no other program bit -- anywhere but variant 5 with doorbells) */
 int rlo_kernel_pick(int kernel, int variant, uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]);
+/* introspection (no GPU): the forwarding tables the storm kernel fills for rank `rank` of an n-rank world, by the
+ * function the kernel itself calls.  below[o] / above[o]: the out-rings a message of origin o goes to when it came
+ * over a ring from a sender at or below / beyond the rank's last_wall; bit 2j + vc = child send_list[j] (rlo_topology)
+ * on virtual channel vc.  RLO_E_INVAL: n < 2, no such rank, a null array */
+int rlo_need_table(int n, int rank, uint32_t* below, uint32_t* above);
 int rlo_host_bulk_stage(rlo_world_t* w, int rank, const void* data, uint64_t len, uint32_t timeout_us, uint32_t* q);
 int rlo_host_bulk_copy(rlo_world_t* w, int rank, const rlo_log_rec_t* ev, void* dst);
 

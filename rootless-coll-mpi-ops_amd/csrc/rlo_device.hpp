@@ -77,6 +77,8 @@ enum Mode : uint32_t {
     MODE_SEND = 1048576u,   // the send program (rlo_hop.hip, the SEND instantiations only): bcasts of caller-owned device buffers
     MODE_SENDB = 2097152u,  // the bulk send program (the progress kernel's bulk-send instantiation only): closed-loop bcasts
                             //   of caller-owned device buffers as bulk messages; the kernel runs it with MODE_LAT set too
+    MODE_NOTAB = 4194304u,  // diagnostics build, A/B and test: the storm kernel computes every ring message's out-rings
+                            //   (kids_of / need_of) instead of reading its forwarding tables
     MODE_CORRUPT = 65536u,  // diagnostics build, test of the VERIFY check: a direct scatter zeroes one granule of one copy
     MODE_HOST = 128u,  // host-service: originations / judge verdicts come from a host command ring,
                        //   deliveries / judge requests / results go to a host pickup ring (rootless_ops.h)

@@ -922,6 +922,20 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     constexpr uint32_t kPair = W == 4 ? 2u : 1u;  // units in registers at once
 
     const uint32_t s2_units = P.stage2_bytes >> 10;
+    // kStorm8: the 8-wave storm kernel (the flagship's).  An 8-wave world's slots hold <= 8 chunks and are staged
+    // whole (plan_lds: 8 waves only for slots of <= 8 chunks, nsmall = the slot), so no message of it is large: this
+    // instantiation has no large-message path (a header that claims more chunks than nsmall is a bad slot), and the
+    // stage2 area holds its forwarding tables instead -- the out-rings of a ring message of origin o, [o] from a
+    // sender at or below last_wall, [n + o] from one beyond it (ring_need, 16 bits an entry).  Filled once per
+    // launch: the tree is fixed for the life of the world, and kids_of / need_of per message were two serial loops
+    // over the send list (a wall rank: 8 entries) in every classification
+    constexpr bool kStorm8 = W == 8 && !BULK && !LL && !PH && PM == kPmStorm;
+    [[maybe_unused]] uint16_t* const ntab = reinterpret_cast<uint16_t*>(stage2);
+#ifdef RLO_DIAG
+    [[maybe_unused]] const bool fwd_tab = kStorm8 && 4u * (uint32_t)P.n <= P.stage2_bytes && !(P.mode & MODE_NOTAB);
+#else
+    [[maybe_unused]] const bool fwd_tab = kStorm8 && 4u * (uint32_t)P.n <= P.stage2_bytes;
+#endif
 #define STG(c, q) (stage + (((uint32_t)(c) * nsmall + (uint32_t)(q)) << 4))
 #define OL(oi, r) olist[(uint32_t)(oi) * (uint32_t)kMaxCand + (uint32_t)(r)]
     // the pending entry of (origin, pool slot) (rlo_device.hpp Params.pend_slots)
@@ -1028,6 +1042,23 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     const uint32_t sl_r = lane < sll ? (uint32_t)t.send_list[lane] : 0u;
     const bool sys = P.sys_scope != 0;
     const uint32_t oring_bytes = P.fwd_cap * P.fwd_stride;
+    // the forwarding tables (kStorm8, above), an origin per thread; a local origination goes to every child, its
+    // out-rings computed once too (need_own).  No tables where they do not fit the stage2 area or a mask does not fit
+    // 16 bits (a rank of > 8 children: worlds over several GPUs), and the diagnostics build's RLO_NO_NEED_TABLE:
+    // classification then computes per message, as every other instantiation does.  (The entries are read in phase D,
+    // barriers later.)
+    [[maybe_unused]] bool use_tab = false;
+    [[maybe_unused]] uint32_t need_own = 0;
+    if constexpr (kStorm8) {
+        use_tab = fwd_tab && nout <= 16;
+        if (use_tab) {
+            for (int o = tid; o < P.n; o += kBlock) {
+                ntab[o] = (uint16_t)ring_need(me, o, false, level, scc, sll, t.send_list);
+                ntab[P.n + o] = (uint16_t)ring_need(me, o, true, level, scc, sll, t.send_list);
+            }
+            need_own = need_of_u((1u << sll) - 1u, me, sll, sl_r, lane);
+        }
+    }
     // wave 0 owns the ring counters: lane g = in-ring g, lane oi = out-ring oi, lane j = vote ring j;
     // each counter is published by a store into the part that polls it
     // remote counter / ring addresses are read from the LDS copy of the topology where they are
@@ -2496,6 +2527,14 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
             int from = -1, judge = 1;
             bool want_jreq = false;  // host mode: a proposal whose verdict has not been asked for yet
             [[maybe_unused]] uint32_t bdesc_len = 0, bdesc_q = 0;  // a local bulk origination's descriptor
+            // a ring message's children -- or, with the forwarding tables, its out-rings at once (need_t; a level-0
+            // rank forwards nothing and reads nothing)
+            // (an expression whose condition is a constant everywhere else: the other instantiations compile to the
+            // code they had)
+            [[maybe_unused]] uint32_t need_t = 0;
+#define RING_KIDS(o)                                                                                                    \
+    ((kStorm8 && use_tab) ? (need_t = level > 0 ? (uint32_t)ntab[(from > last_wall ? (uint32_t)P.n : 0u) + (uint32_t)(o)] : 0u, 0u) \
+                          : kids_of(me, (o), from, level, last_wall, scc, sll, sl_r))
             if (active && c < R) {
                 const u32x4 h = *reinterpret_cast<const u32x4*>(STG(c, 0));
                 group = S.cand[c].group;
@@ -2516,8 +2555,11 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 } else if (origin >= P.n || (tag == TAG_BCAST && (PMODE(MODE_LAT)) && id >= P.lat_rounds)) {
                     set_error(S, P, ERR_BAD_SLOT, w0);
                     kind = K_BAD;  // consumed, never forwarded, no side effects
+                } else if (kStorm8 && ((kHdr + (w2 & 0xffffu) + 15u) >> 4) > nsmall) {
+                    set_error(S, P, ERR_BAD_SLOT, w0);  // longer than a slot of this world: no sender wrote that
+                    kind = K_BAD;
                 } else if (tag == TAG_BCAST || tag == TAG_DECISION || (BULK && tag == TAG_BULK)) {
-                    kids = kids_of(me, origin, from, level, last_wall, scc, sll, sl_r);
+                    kids = RING_KIDS(origin);
                 } else if (tag == TAG_PROPOSAL) {
                     // PBuf [pid][vote][data_len u64][data] at slot + 16 (rootless_ops.c:1402-1410)
                     const uint32_t plen = w2 & 0xffffu;
@@ -2540,7 +2582,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                         if (dl > plen - 16u) dl = plen > 16u ? plen - 16u : 0u;
                         judge = judge_eval(P, rf, me, my_mask, (int32_t)id, src + kHdr + 16u, dl);
                     }
-                    kids = judge == 1 ? kids_of(me, origin, from, level, last_wall, scc, sll, sl_r) : 0u;
+                    kids = judge == 1 ? RING_KIDS(origin) : 0u;
                 } else {
                     set_error(S, P, ERR_BAD_SLOT, w0);
                     kind = K_BAD;
@@ -2621,6 +2663,11 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 // carries the slot mark every hop checks
                 w2 = (w2 & 0xff00ffffu) | (kSlotMark << 16);
                 const uint32_t nch = (kHdr + (w2 & 0xffffu) + 15u) >> 4;
+                if (kStorm8 && nch > nsmall) {  // (no program of an 8-wave world originates one)
+                    set_error(S, P, ERR_BAD_SLOT, w0);
+                    kind = K_BAD;
+                    kids = 0;
+                }
                 *reinterpret_cast<u32x4*>(STG(c, 0)) = u32x4{w0, id, w2, t0};
                 if (BULK && bdesc_len) {  // the announcement's payload: {len, bulk sequence}
                     *reinterpret_cast<u32x4*>(STG(c, 1)) = u32x4{bdesc_len, bdesc_q, 0u, 0u};
@@ -2631,7 +2678,9 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 }
             }
             const int origin = (int)(w0 & 0xffffu);
-            const uint32_t need = active ? need_of(kids, origin, sll, sl_r) : 0u;
+#undef RING_KIDS
+            const uint32_t need = (kStorm8 && use_tab) ? (!active ? 0u : (c < R ? need_t : (kids ? need_own : 0u)))
+                                                       : (active ? need_of(kids, origin, sll, sl_r) : 0u);
             for (uint64_t jb = __ballot(want_jreq); jb; jb &= jb - 1) {  // host judge requests (uniform loop)
                 const int l = __builtin_ctzll(jb);
                 const uint32_t lsrc = rdl32(src, l), lw2 = rdl32(w2, l), lid = rdl32(id, l);
@@ -2691,7 +2740,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
             const bool admitted = active && fits && c < S.first_bad[group];
             const uint32_t an = admitted ? need : 0u;
             const uint32_t len = w2 & 0xffffu;
-            const bool isbig = admitted && ((kHdr + len + 15u) >> 4) > nsmall;
+            const bool isbig = kStorm8 ? false : admitted && ((kHdr + len + 15u) >> 4) > nsmall;
             const uint32_t nch_s = (kHdr + len + 15u) >> 4;  // small path: chunks, kept in the olist entry
             const uint32_t wadm = wave_or(an);
             // this wave's admitted count per out-ring differs from its wanted count (wcnt, above) only
@@ -2702,7 +2751,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 if (lane == 0) S.wcnt[w][oi] = (uint32_t)__popcll(b);
             }
             {  // chunks per message on the small copy path this iteration (storm: all equal)
-                const uint32_t mx = wave_max(admitted && !isbig ? (kHdr + len + 15u) >> 4 : 0u);
+                // (kStorm8: a bad header's length counts for nothing)
+                const uint32_t mx = wave_max((kStorm8 ? admitted && kind != K_BAD : admitted && !isbig) ? (kHdr + len + 15u) >> 4 : 0u);
                 if (lane == 0 && mx) atomicMax(&S.nchmax, mx);
             }
             BAR();
@@ -2774,7 +2824,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                                 ps->valid = PS_NONE;
                                 emit_vote<LL>(S, P, me, (uint32_t)k, origin, pid, pseq, 0);
                             } else {
-                                const uint32_t nk = (uint32_t)__builtin_popcount(kids);
+                                // (one out-ring per child: with the forwarding tables `need` stands for `kids`)
+                                const uint32_t nk = (uint32_t)__builtin_popcount(kStorm8 ? need : kids);
                                 ps->pid = pid;
                                 ps->word = 0;
                                 ps->parent_k = (uint16_t)k;
@@ -2913,7 +2964,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 }
                 if (PMODE(MODE_PROF)) {
                     uint32_t tot;
-                    wave_excl_scan(admitted ? (uint32_t)__builtin_popcount(kids) : 0u, &tot);
+                    wave_excl_scan(admitted ? (uint32_t)__builtin_popcount(kStorm8 ? need : kids) : 0u, &tot);
                     if (lane == 0) atomicAdd((unsigned long long*)&S.dbg[6], (unsigned long long)tot);
                 }
             }
@@ -2926,7 +2977,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
             // ---------------- G1: stage the first round of large-message groups (before any store)
             // (the 8-wave doorbell instantiation runs programs whose every message takes the small path:
             // the host sets MODE_LL only then, rlo_world.cpp ll_mode; 8-wave worlds have small slots anyway)
-            const uint32_t nbig = (LL && W == 8) ? 0u : S.nbig;
+            // (kStorm8, above: no large messages, and the tables live in stage2)
+            const uint32_t nbig = ((LL && W == 8) || kStorm8) ? 0u : S.nbig;
             // staging rounds of all of stage2: load -> store -> wait.  (MODE_PIPE, A/B: two halves, round r+1's
             // loads in flight while round r is stored -- measured slower, the rounds halve)
             const bool pipe = s2_units >= 2u * kSubMax && (PMODE(MODE_PIPE));
@@ -3500,6 +3552,22 @@ extern "C" hipError_t rlo_launch_progress(int row, const rlo::Params* p, int blo
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kProgressRows[row].kernel, dim3(blocks), dim3(64 * kProgressRows[row].w), dyn_lds, stream, *p);
     return hipGetLastError();
+}
+
+// the storm kernel's forwarding tables of one rank, on the host (rlo_hip.h): ring_need is the function the kernel fills
+// its own with
+extern "C" int rlo_topology(int n, int rank, int* level, int* last_wall, int* scc, int* sll, int* send_list);
+extern "C" int rlo_need_table(int n, int rank, uint32_t* below, uint32_t* above) {
+    int level = 0, scc = 0, sll = 0;
+    int32_t send_list[rlo::kMaxFanout];
+    if (!below || !above) return -1;  // RLO_E_INVAL
+    const int rc = rlo_topology(n, rank, &level, nullptr, &scc, &sll, send_list);
+    if (rc) return rc;
+    for (int o = 0; o < n; o++) {
+        below[o] = rlo::ring_need(rank, o, false, level, scc, sll, send_list);
+        above[o] = rlo::ring_need(rank, o, true, level, scc, sll, send_list);
+    }
+    return 0;
 }
 
 extern "C" size_t rlo_kernel_static_lds(int variant) {

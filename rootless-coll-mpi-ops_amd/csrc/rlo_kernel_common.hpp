@@ -306,7 +306,7 @@ __device__ __forceinline__ uint32_t mask_bytes(uint32_t w, int keep) {  // keep 
 }
 
 // rootless_ops.c:1534-1556
-__device__ __forceinline__ bool passed_origin(int me, int origin, int to) {
+__host__ __device__ __forceinline__ bool passed_origin(int me, int origin, int to) {
     if (to == origin) return true;
     if (me >= origin) {
         if (to > me) return false;
@@ -335,6 +335,21 @@ __device__ __forceinline__ uint32_t need_of(uint32_t kids, int origin, int sll, 
     uint32_t need = 0;
     for (int j = 0; j < sll; j++)
         if ((kids >> j) & 1u) need |= 1u << (2 * j + ((int)rdl32(sl_r, j) < origin ? 1 : 0));
+    return need;
+}
+
+// the two in one, for a message that came over a ring (from >= 0), on the host as well: need_of(kids_of(...)) bit for
+// bit.  Of the sender only `beyond` (from > last_wall) matters, so a rank's out-ring mask is a function of (origin,
+// beyond) for the life of the world: the forwarding tables (rlo_kernel.hip, rlo_need_table) hold it.  send_list:
+// the rank's sll children, wherever the caller keeps them
+__host__ __device__ __forceinline__ uint32_t ring_need(int me, int origin, bool beyond, int level, int scc, int sll,
+                                                       const int32_t* send_list) {
+    if (level <= 0) return 0u;
+    uint32_t need = 0;
+    for (int j = 0; j < sll; j++) {
+        const int to = send_list[j];
+        if (beyond ? j <= scc : (j < scc && !passed_origin(me, origin, to))) need |= 1u << (2 * j + (to < origin ? 1 : 0));
+    }
     return need;
 }
 

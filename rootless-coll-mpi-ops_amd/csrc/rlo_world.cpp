@@ -2087,6 +2087,7 @@ static uint32_t diag_modes(uint32_t mode) {
         {"RLO_BULK_CORRUPT", rlo::MODE_CORRUPT},  // test: VERIFY must catch a zeroed granule
         {"RLO_NO_HPOLLER", rlo::MODE_NOHPW},      // A/B: no wave-1 host poller
         {"RLO_HOST_DIAG", rlo::MODE_HDIAG},       // diagnostic: command-wait counters
+        {"RLO_NO_NEED_TABLE", rlo::MODE_NOTAB},   // A/B, test: the storm kernel computes out-rings per message
     };
     static const uint32_t on = [] {  // read once per process
         uint32_t m = 0;

@@ -146,7 +146,7 @@ EXPORTS = ["rlo_topology", "rlo_children", "rlo_world_create", "rlo_world_destro
            "rlo_storm_lengths", "rlo_host_share", "rlo_host_unlink", "rlo_host_proxy", "rlo_host_wait_started",
            "rlo_host_fail", "rlo_client_attach", "rlo_client_detach", "rlo_client_state", "rlo_client_post",
            "rlo_client_poll", "rlo_client_cmd_count", "rlo_client_bulk_put", "rlo_client_bulk_get", "rlo_client_debug", "rlo_client_hdiag", "rlo_client_fwd", "rlo_host_device_judge",
-           "rlo_pool_trim", "rlo_pool_stats", "rlo_kernel_pick"]
+           "rlo_pool_trim", "rlo_pool_stats", "rlo_kernel_pick", "rlo_need_table"]
 
 _lib = None
 
@@ -208,6 +208,7 @@ def load():
                                     ctypes.POINTER(ctypes.c_uint32)]
     L.rlo_kernel_pick.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
                                   ctypes.POINTER(ctypes.c_uint32)]
+    L.rlo_need_table.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.rlo_host_device_judge.argtypes = [vp, ctypes.POINTER(IarCfg)]
     L.rlo_host_share.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint64]
     L.rlo_host_unlink.argtypes = [vp]

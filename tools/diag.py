@@ -25,7 +25,7 @@ def report(name, w, ms, deliveries):
           % (dur.min(), np.median(dur), dur.max(), busy.min(), np.median(busy), busy.max(), st["stalls"].max(),
              int(np.argmax(st["stalls"]))))
     dbg = st["dbg"].astype(np.float64)
-    for r in sorted(set([0, 1, 2, 128, 255, int(np.argmax(st["stalls"]))])):
+    for r in sorted(set(x for x in (0, 1, 2, 128, 224, 255, int(np.argmax(st["stalls"]))) if x < len(dbg))):
         d = dbg[r]
         print("   rank %3d: iters %d busy %d | ring cands %.0f admitted %.0f | storm-allowed iters %.0f | "
               "large rounds: drain cycles %.0f, rounds (push) / relay-full pushes (pull) %.0f (%.0f cycles/round) | "
