@@ -302,6 +302,40 @@ int rlo_program_send_bulk(rlo_world_t* w, const rlo_send_bulk_cfg_t* cfg);
 /* the argument checks of rlo_program_send_bulk that need no GPU (pure host): RLO_OK or RLO_E_INVAL */
 int rlo_send_bulk_check(const rlo_send_bulk_cfg_t* cfg, int n_ranks, uint64_t bulk_max);
 
+/* storm send: rootless bcasts of caller-owned device buffers AT STORM RATE, on the progress kernel.  k messages from
+ * any ranks in any mix, open loop: every rank originates its own messages, up to `window` per iteration, as fast as
+ * its out-rings take them (per-origin FIFO holds, as for the storm; there is no total order).  Message i is a
+ * reference-style bcast (tag BCAST, header id i, origin origin[i]) whose payload the origin's workgroup reads from
+ * `src` in device memory; every rank but the origin writes the payload it receives to its place in `dst`: bytes
+ * [0, len) are the source's, [len, round16(len)) zero, and nothing else in dst is written (the rest of the place, the
+ * gap up to rank_stride, the origin's own place).  No byte crosses the host.  Messages up to the small copy path's 24
+ * chunks travel as ring slots, longer ones (worlds of 4 waves) on the large-message path, pulled or pushed as the
+ * world's.  rlo_stats: bcast_delivered, originated, bcast_sum (the storm's per-message checksum), error.  RLO_FLAG_LOG:
+ * the delivery records (origin, tree parent, id, len) without payload copies -- dst is the payload.
+ * RLO_E_INVAL, before anything is uploaded or reset: a world with bulk messages (rlo_program_send_bulk is its
+ * program), a RLO_PART_ONE_XCD world, a message longer than the world's max_payload, and any argument outside the
+ * ranges below.  On the device a ring message that cannot be one of the program's (id >= k, len > slot, another tag)
+ * raises RLO_DERR_BAD_SLOT before any store to dst.  Worlds of several parts in one process: each part passes its
+ * own src and dst. */
+typedef struct {
+    int64_t k;              /* messages, 1 .. 2^32-1 (the storm's id width)                                          */
+    const int32_t* origin;  /* host [k]: the rank that originates message i (any rank, any mix)                      */
+    const uint32_t* len;    /* host [k]: bytes of message i, 1 .. slot; NULL = every message is `slot` bytes         */
+    const void* src;        /* DEVICE, 16-B aligned: message i's bytes at src + i * slot, readable for
+                               round16(len[i]) bytes.  This part reads only the messages its own ranks originate.
+                               Must not change while the launch runs                                               */
+    void* dst;              /* DEVICE, 16-B aligned: local rank lr's copy of message i at lr * rank_stride + i * slot */
+    uint32_t slot;          /* bytes per message place: a multiple of 16, <= the world's max_payload rounded up to 16 */
+    uint32_t window;        /* as rlo_storm_cfg_t.window (0 = 64)                                                    */
+    uint64_t rank_stride;   /* bytes between ranks in dst: a multiple of 16; 0 = k * slot; >= (k - 1) * slot +
+                               round16(len[k - 1])                                                                 */
+    uint32_t flags;         /* RLO_FLAG_LOG | RLO_FLAG_HIST | RLO_FLAG_PROF                                          */
+    uint32_t log_cap;
+} rlo_send_storm_cfg_t;
+int rlo_program_send_storm(rlo_world_t* w, const rlo_send_storm_cfg_t* cfg);
+/* the argument checks of rlo_program_send_storm that need no GPU (pure host): RLO_OK or RLO_E_INVAL */
+int rlo_send_storm_check(const rlo_send_storm_cfg_t* cfg, int n_ranks, uint32_t max_payload);
+
 #define RLO_JUDGE_APPROVE 0u /* approve everything                                           */
 #define RLO_JUDGE_MASK 1u    /* decline iff mask[rank] != 0 (arg != NULL)                     */
 #define RLO_JUDGE_ISP 2u     /* testcases.c:18-37 is_proposal_approved_cb, per-rank string    */
@@ -433,7 +467,9 @@ int rlo_storm_lengths(uint64_t seed, uint64_t k, uint32_t len, uint32_t len_max,
  * with bulk messages (progress only); mode: the launch's mode bits (rlo_device.hpp Mode); pend_hbm, sys_scope: as
  * rlo_world_info_t.  out: the instantiation's template arguments -- progress {W, BULK, LL, PH, program mask}, hop
  * {PH, SYS, LOC, SEND, 0}.  RLO_E_INVAL: no such kernel (the hop kernel's send program, or system scope, on one XCD;
- * the bulk send program -- mode MODE_SENDB | MODE_LL, no other program bit -- anywhere but variant 5 with doorbells) */
+ * the bulk send program -- mode MODE_SENDB | MODE_LL, no other program bit -- anywhere but variant 5 with doorbells;
+ * the storm send program -- mode MODE_SENDS, no other program bit and no doorbells: the storm-send instantiation of
+ * variant 8 or 4 -- on variant 5).  Beside a program bit (storm, latency, iar, host) neither send bit changes the pick */
 int rlo_kernel_pick(int kernel, int variant, uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]);
 /* introspection (no GPU): the forwarding tables the storm kernel fills for rank `rank` of an n-rank world, by the
  * function the kernel itself calls.  below[o] / above[o]: the out-rings a message of origin o goes to when it came

@@ -79,6 +79,8 @@ enum Mode : uint32_t {
                             //   of caller-owned device buffers as bulk messages; the kernel runs it with MODE_LAT set too
     MODE_NOTAB = 4194304u,  // diagnostics build, A/B and test: the storm kernel computes every ring message's out-rings
                             //   (kids_of / need_of) instead of reading its forwarding tables
+    MODE_SENDS = 8388608u,  // the storm send program (the progress kernel's storm-send instantiations only): open-loop bcasts of
+                            //   caller-owned device buffers at storm rate; the kernel runs it with MODE_STORM set too
     MODE_CORRUPT = 65536u,  // diagnostics build, test of the VERIFY check: a direct scatter zeroes one granule of one copy
     MODE_HOST = 128u,  // host-service: originations / judge verdicts come from a host command ring,
                        //   deliveries / judge requests / results go to a host pickup ring (rootless_ops.h)
@@ -315,6 +317,10 @@ struct Params {
     // the bulk send program (MODE_SENDB; appended likewise): message i's bytes at send_src + i * send_stride, local rank
     // lr's copy at send_dst + lr * send_rank_stride + i * send_stride (send_slot unused)
     uint64_t send_stride, send_rank_stride;
+    // the storm send program (MODE_SENDS; appended likewise): the own lists are sched_off / sched_ids (the storm's);
+    // sched_len runs beside sched_ids.  Message i's bytes at send_src + i * send_slot, local rank lr's copy at
+    // send_dst + lr * send_rank_stride + i * send_slot
+    const uint32_t* sched_len;      // [sched_ids entries] bytes of each own message
 };
 
 // ---- bulk messages (longer than a ring slot; SURVEY §8(f)1, BASELINE configs[2], [4]).

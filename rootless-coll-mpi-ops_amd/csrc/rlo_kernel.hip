@@ -476,6 +476,20 @@ __device__ __forceinline__ u32x4 storm_granule(uint32_t origin, uint32_t bid, ui
                  mask_bytes((uint32_t)(b >> 32), b0 - 12)};
 }
 
+// the storm send program (MODE_SENDS): payload chunk p (p < ceil(len / 16): nothing past round16(len) of a message is
+// read) of own message `id` from the caller's source, the bytes from len on zero; and a delivered payload chunk into
+// this rank's place of the caller's destination (plain stores: nothing in the launch reads them).  64-bit addresses:
+// k * slot may exceed 4 GiB
+typedef __attribute__((address_space(1))) u32x4 gu32x4;
+__device__ __forceinline__ u32x4 ss_get(const Params& P, uint32_t id, uint32_t len, uint32_t p) {
+    const u32x4 v = *(const gu32x4*)(reinterpret_cast<uint64_t>(P.send_src) + (uint64_t)id * P.send_slot + 16ull * p);
+    const int b0 = (int)len - (int)(16u * p);
+    return u32x4{mask_bytes(v.x, b0), mask_bytes(v.y, b0 - 4), mask_bytes(v.z, b0 - 8), mask_bytes(v.w, b0 - 12)};
+}
+__device__ __forceinline__ void ss_put(const Params& P, int lr, uint32_t id, uint32_t p, u32x4 v) {
+    *(gu32x4*)(reinterpret_cast<uint64_t>(P.send_dst) + (uint64_t)lr * P.send_rank_stride + (uint64_t)id * P.send_slot + 16ull * p) = v;
+}
+
 // A mover workgroup: draws sub-jobs of its class by ticket (one fetch-add, never retried: the
 // claim rate no longer serialises on one word), waits for the ticket's record, and moves every tile
 // of it.  A slot is freed as soon as its record is read, except a VERIFY job's first slot, whose
@@ -871,6 +885,9 @@ constexpr uint32_t kPmStorm = ~(uint32_t)(MODE_LAT | MODE_IAR | MODE_HOST);
 constexpr uint32_t kPmHost = ~(uint32_t)(MODE_STORM | MODE_LAT);  // the drop-in's host service (MODE_HOST | MODE_IAR)
 // the bulk send program (MODE_SENDB, launched with MODE_LAT: the latency program's closed loop); it has no timeline
 constexpr uint32_t kPmSendBulk = ~(uint32_t)(MODE_STORM | MODE_IAR | MODE_HOST | MODE_TL | MODE_CORRUPT);
+// the storm send program (MODE_SENDS, launched with MODE_STORM: the storm's open loop over the caller's buffers); it
+// has no timeline, no doorbells, none of the other send programs' code and no host diagnostics (S.hd is its own)
+constexpr uint32_t kPmStormSend = ~(uint32_t)(MODE_LAT | MODE_IAR | MODE_HOST | MODE_TL | MODE_LL | MODE_SEND | MODE_SENDB | MODE_HDIAG);
 
 // PH: the pending-proposal tables live in HBM (Params.pend_hbm; worlds whose N x pool entries would crowd
 // the small copy path's stage out of LDS: the 8-GPU worlds), instantiated for the programs that hold
@@ -890,6 +907,16 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     // BS: the bulk send program's instantiation.  Every message is a bulk message whatever its length; its id and
     // length come from the rank's own list (lat_own, send_own_len) instead of the round number and P.len
     constexpr bool BS = BULK && PM == kPmSendBulk;
+    // SS: the storm send program's instantiations.  A local origination's length comes from the rank's own list
+    // (sched_len), its payload from the caller's source; every delivered payload chunk goes to the caller's destination
+    constexpr bool SS = !BULK && !LL && !PH && PM == kPmStormSend;
+    // A/B build (make AB=... ABFLAGS=-DRLO_AB_SS_PACKED), the 8-wave storm-send kernel: dst as one more destination of
+    // the small copy path's packed (message, chunk) item walk instead of the per-lane pickup loop
+#ifdef RLO_AB_SS_PACKED
+    constexpr bool kSSPacked = SS && W == 8;
+#else
+    constexpr bool kSSPacked = false;
+#endif
 #define LAT_IS_BULK (BS || P.len > P.ring_cap)
     constexpr uint32_t kHostBase = kMaxCand - kPass;  // host mode: command run staged at the last 64 candidates
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
@@ -929,7 +956,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     // sender at or below last_wall, [n + o] from one beyond it (ring_need, 16 bits an entry).  Filled once per
     // launch: the tree is fixed for the life of the world, and kids_of / need_of per message were two serial loops
     // over the send list (a wall rank: 8 entries) in every classification
-    constexpr bool kStorm8 = W == 8 && !BULK && !LL && !PH && PM == kPmStorm;
+    constexpr bool kStorm8 = W == 8 && !BULK && !LL && !PH && (PM == kPmStorm || PM == kPmStormSend);
     [[maybe_unused]] uint16_t* const ntab = reinterpret_cast<uint16_t*>(stage2);
 #ifdef RLO_DIAG
     [[maybe_unused]] const bool fwd_tab = kStorm8 && 4u * (uint32_t)P.n <= P.stage2_bytes && !(P.mode & MODE_NOTAB);
@@ -1176,6 +1203,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
         bool ok = ((fw2 >> 16) & 0xffu) == kSlotMark && forg < P.n && fnch <= nsmall &&
                   (ftag == TAG_BCAST || ftag == TAG_DECISION || ftag == TAG_PROPOSAL || (BULK && ftag == TAG_BULK)) &&
                   !(ftag == TAG_BCAST && (PMODE(MODE_LAT)) && fid >= P.lat_rounds);
+        // storm send: a message that cannot be one of the program's is the full path's (ERR_BAD_SLOT there)
+        if constexpr (SS) ok = ok && ftag == TAG_BCAST && fid < P.send_k && flen <= P.send_slot;
         int fjudge = 1;
         uint32_t fkids = 0, fneed = 0;
         uint32_t flog = ~0u;
@@ -1255,6 +1284,9 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
             if (q < fnch)
                 acc_sum += q == 0 ? chunk_mix(0xFFFFFFFFu, u32x4{(uint32_t)forg, fid, TAG_BCAST, flen})
                                   : chunk_mix(q - 1u, v);
+            if constexpr (SS) {
+                if (q >= 1u && q < fnch) ss_put(P, lr, fid, q - 1u, v);
+            }
         } else if (ftag == TAG_PROPOSAL) {  // _iar_proposal_handler :668-726
             if (lane == 0) {
                 atomicAdd(&S.proposals_recv, 1ull);
@@ -1821,6 +1853,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
         // ---------------- A: wave 0 polls; every wave drains its stores of the last iteration
         uint64_t in_tail_r = 0, out_head_r = 0, vin_tail_r = 0, vout_head_r = 0;
         uint32_t errf = 0, sid = 0, latr = 0;
+        [[maybe_unused]] uint32_t slen = 0;  // storm send: the length of own message sid
         if (w == 0) {
             // After an iteration that selected nothing, wave 0 re-polls in a tight loop until a
             // polled word moves (the other waves wait at the barrier): a message arriving at an
@@ -1930,6 +1963,9 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
             if ((PMODE(MODE_LAT)) && me == 0) lat_observe(latr);
             if ((PMODE(MODE_STORM)) && sched_next + lane < sched_n && (uint32_t)lane < P.window)
                 sid = P.sched_ids[sched_base + sched_next + lane];
+            if constexpr (SS) {
+                if (sched_next + lane < sched_n && (uint32_t)lane < P.window) slen = P.sched_len[sched_base + sched_next + lane];
+            }
         } else if (hpw && w == 1) {
             // the host poller: until wave 0 ends its spin, the next command's doorbell (16 B to each of lanes 0-15,
             // to LDS at kLLCmdBell: the doorbell pass checks its tags) and the command tail / pickup head (-> S.hp),
@@ -2329,6 +2365,11 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                     nstorm = ww;
                     C += ww;
                     if ((uint32_t)lane < ww) S.storm_ids[lane] = sid;
+                    // storm send: the length travels to classification in the candidate's own stage slot (nothing
+                    // else writes it before phase D stages the header there: ring candidates are [0, R), R <= C)
+                    if constexpr (SS) {
+                        if ((uint32_t)lane < ww) *reinterpret_cast<uint32_t*>(STG(storm_base + (uint32_t)lane, 0)) = slen;
+                    }
                 }
             }
             if ((PMODE(MODE_LAT)) && C < kMaxCand) {
@@ -2558,6 +2599,9 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 } else if (kStorm8 && ((kHdr + (w2 & 0xffffu) + 15u) >> 4) > nsmall) {
                     set_error(S, P, ERR_BAD_SLOT, w0);  // longer than a slot of this world: no sender wrote that
                     kind = K_BAD;
+                } else if (SS && (tag != TAG_BCAST || id >= P.send_k || (w2 & 0xffffu) > P.send_slot)) {
+                    set_error(S, P, ERR_BAD_SLOT, w0);  // not one of the program's messages: nothing of it reaches send_dst
+                    kind = K_BAD;
                 } else if (tag == TAG_BCAST || tag == TAG_DECISION || (BULK && tag == TAG_BULK)) {
                     kids = RING_KIDS(origin);
                 } else if (tag == TAG_PROPOSAL) {
@@ -2596,6 +2640,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                     id = S.storm_ids[c - storm_base];
                     w0 = (uint32_t)me | (TAG_BCAST << 16) | (0xffu << 24);
                     w2 = P.len;
+                    if constexpr (SS) w2 = *reinterpret_cast<const uint32_t*>(STG(c, 0));  // (the window put it there)
                     if constexpr (BULK) {
                         const uint32_t bq = S.b.bq[c - storm_base];
                         w2 = S.b.blen[c - storm_base];
@@ -2672,9 +2717,14 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 if (BULK && bdesc_len) {  // the announcement's payload: {len, bulk sequence}
                     *reinterpret_cast<u32x4*>(STG(c, 1)) = u32x4{bdesc_len, bdesc_q, 0u, 0u};
                 } else if (nch <= nsmall && kind != K_HOST && kind != K_BAD) {
+                    if constexpr (SS) {  // the caller's bytes (kind is K_STORM: the program originates nothing else)
+                        for (uint32_t q = 1; q < nch; q++)
+                            *reinterpret_cast<u32x4*>(STG(c, q)) = ss_get(P, id, w2 & 0xffffu, q - 1u);
+                    } else {
                     for (uint32_t q = 1; q < nch; q++)
                         *reinterpret_cast<u32x4*>(STG(c, q)) =
                             gen_chunk(P, kind, me, id, w2 & 0xffffu, src, (int)(int8_t)(w0 >> 24), q);
+                    }
                 }
             }
             const int origin = (int)(w0 & 0xffffu);
@@ -2755,7 +2805,31 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 const uint32_t mx = wave_max((kStorm8 ? admitted && kind != K_BAD : admitted && !isbig) ? (kHdr + len + 15u) >> 4 : 0u);
                 if (lane == 0 && mx) atomicMax(&S.nchmax, mx);
             }
+            // storm send with a log: the delivery records are written in candidate order (an in-ring's messages in
+            // ring order, a wave's block of records after the lower waves'), so the log shows every origin's messages
+            // in the order they were delivered -- log_put's per-lane tickets order the waves of one iteration
+            // arbitrarily.  Each wave's count of deliveries travels in S.hd (the host service's diagnostics words:
+            // no host mode in this instantiation)
+            [[maybe_unused]] uint64_t ss_dmask = 0;
+            if constexpr (SS) {
+                if (kSSPacked || (PMODE(MODE_LOG))) {
+                    ss_dmask = __ballot(admitted && kind == K_RING && ((w0 >> 16) & 0xffu) == TAG_BCAST);
+                    if (lane == 0) S.hd[w] = (uint64_t)__popcll(ss_dmask);
+                }
+            }
             BAR();
+            [[maybe_unused]] uint32_t ss_log = 0;  // storm send: the log index of this wave's first delivery record
+            if constexpr (SS) {
+                if (kSSPacked || (PMODE(MODE_LOG))) {
+                    uint32_t pre = 0;
+                    for (int v = 0; v < w; v++) pre += (uint32_t)S.hd[v];
+                    ss_log = (uint32_t)S.log_count + pre;
+                    if constexpr (kSSPacked) {  // the delivered messages, in candidate order (S.big: no large messages here)
+                        if ((ss_dmask >> lane) & 1ull)
+                            S.big[pre + (uint32_t)__popcll(ss_dmask & lt_mask)] = (uint16_t)(c | (nch_s << 9));
+                    }
+                }
+            }
             uint32_t pre_r = 0;  // lane oi: slots of out-ring oi taken by lower waves
             if (lane < nout) {
                 uint32_t tot = 0;
@@ -2800,6 +2874,18 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                             }
                         }
                         // aux: device ticks (10 ns) from origination to this pickup (latency diagnostics)
+                        if constexpr (SS) {  // (a record without a payload copy, at its place in candidate order)
+                            if (PMODE(MODE_LOG)) {
+                                const uint32_t li = ss_log + (uint32_t)__popcll(ss_dmask & lt_mask);
+                                if (li >= P.log_cap) {
+                                    set_error(S, P, ERR_LOG_FULL, li);
+                                } else {
+                                    u32x4* lp = reinterpret_cast<u32x4*>(&P.log[(size_t)lr * P.log_cap + li]);
+                                    st_sys16(lp, u32x4{LOG_DELIVER | (TAG_BCAST << 8), (uint32_t)origin, (uint32_t)from, id});
+                                    st_sys16(lp + 1, u32x4{len, ~0u, (uint32_t)now_ticks() - t0, ~0u});
+                                }
+                            }
+                        } else
                         logidx = log_put<PM>(S, P, lr, LOG_DELIVER | (TAG_BCAST << 8), origin, from, id, len, -1,
                                          (uint32_t)now_ticks() - t0);
                     } else if (tag == TAG_PROPOSAL) {  // _iar_proposal_handler (:668-726)
@@ -2969,6 +3055,13 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 }
             }
             BAR();  // olist / cand / n_oi / big complete
+            if constexpr (SS) {  // every wave has read the log count: this iteration's delivery records are taken
+                if ((PMODE(MODE_LOG)) && tid == 0) {
+                    uint64_t nrec = 0;
+                    for (int v = 0; v < kWaves; v++) nrec += S.hd[v];
+                    S.log_count += nrec;
+                }
+            }
             PST(4, 7);
             if constexpr (BULK) {
                 if (w == 0) flush_posts(S.b, P, lane);  // this iteration's job posts, before its copies
@@ -3065,6 +3158,9 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                         if (pq < pch)
                             __builtin_amdgcn_raw_ptr_buffer_load_lds(rh, lds_ptr(dst), 16, cl.src + 16u * (pq + 1u), 0, 0, kAuxSc1 | 1);
                     } else if (pq < pch) {
+                        if constexpr (SS)  // the caller's bytes, through registers: the tail of the last chunk is masked
+                            *reinterpret_cast<u32x4*>(dst + 16u * lane) = ss_get(P, cl.id, cl.w2 & 0xffffu, pq);
+                        else
                         *reinterpret_cast<u32x4*>(dst + 16u * lane) =
                             gen_chunk(P, cl.kind, me, cl.id, cl.w2 & 0xffffu, cl.src, (int)(int8_t)(cl.w0 >> 24), pq + 1u);
                     }
@@ -3162,11 +3258,25 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 for (uint32_t q = 1; q < nch; q++) {
                     const u32x4 v = *reinterpret_cast<const u32x4*>(STG(c, q));
                     acc_sum += chunk_mix(q - 1u, v);
+                    if constexpr (SS) {  // this rank's copy, lane = message (records without payload copies: dst is the payload)
+                        if constexpr (!kSSPacked) ss_put(P, lr, id, q - 1u, v);
+                    } else
                     if (logidx != ~0u)
                         st_sys16(P.log_payload + ((size_t)lr * P.log_cap + logidx) * P.log_stride + 16u * (q - 1), v);
                 }
             }
-
+            if constexpr (kSSPacked) {  // the delivered messages' (message, chunk) items, split evenly over the waves
+                uint32_t ndel = 0;
+                for (int v = 0; v < kWaves; v++) ndel += (uint32_t)S.hd[v];
+                const uint32_t nitd = ndel * nq;
+                const uint32_t dlo = nitd * (uint32_t)w / (uint32_t)kWaves, dhi = nitd * (uint32_t)(w + 1) / (uint32_t)kWaves;
+                for (uint32_t i = dlo + (uint32_t)lane; i < dhi; i += 64u) {
+                    const uint32_t r = div_small(i, qmagic), q = i - r * nq;
+                    const uint32_t e = S.big[r], cc = e & 0x1ffu;
+                    if (q >= 1u && q < (e >> 9))
+                        ss_put(P, lr, S.cand[cc].id, q - 1u, *reinterpret_cast<const u32x4*>(STG(cc, q)));
+                }
+            }
 
             // ---------------- G3: large messages, 64 x 16 B per wave store instruction.  The out-rings'
             // bases and start tails lane-distributed (lane oi), a message's slot positions read with one
@@ -3244,6 +3354,7 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                                     const uint32_t pp = pq + 64u * u;
                                     if (u0 + u < nsub && pp < pch) {
                                         acc_sum += chunk_mix(pp, vv[u]);
+                                        if constexpr (SS) ss_put(P, lr, cl.id, pp, vv[u]);  // 64 x 16 B per unit
                                         if (cl.logidx != ~0u && 16u * (pp + 1u) <= P.log_stride)
                                             st_sys16(P.log_payload + ((size_t)lr * P.log_cap + cl.logidx) * P.log_stride + 16u * pp, vv[u]);
                                     }
@@ -3480,7 +3591,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
 // latency program and the iar program (doorbells; the iar one with the LDS or the HBM pending table); bulk worlds --
 // the latency program (C3), the storm (C5) and the bulk send program (kPmSendBulk: the only kernel that runs it, and it
 // runs nothing else); and the host service the drop-in runs (doorbells; every variant, LDS or HBM tables).  PH: programs that hold proposals in a world with HBM pending tables (no bulk worlds: their N x B
-// bound keeps the table small).  (Rows in the order the device code has always been emitted in.)
+// bound keeps the table small).  The storm send program (kPmStormSend) has a row per non-bulk variant without doorbells,
+// the only kernels that run it.  (Rows in the order the device code has always been emitted in: new ones at the end.)
 #define RLO_PROGRESS_ROWS(X)                                                                                     \
     X(8, false, true, true, kPmIar) X(8, false, true, true, kPmHost) X(8, false, true, true, kPmAll)              \
     X(8, false, false, true, kPmAll)                                                                             \
@@ -3490,7 +3602,8 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
     X(4, true, true, false, kPmLat) X(4, true, false, false, kPmStorm) X(4, true, true, false, kPmHost)           \
     X(4, true, true, false, kPmAll) X(4, true, false, false, kPmAll)                                              \
     X(4, true, true, false, kPmSendBulk)                                                                         \
-    X(4, false, true, false, kPmHost) X(4, false, true, false, kPmAll) X(4, false, false, false, kPmAll)
+    X(4, false, true, false, kPmHost) X(4, false, true, false, kPmAll) X(4, false, false, false, kPmAll)              \
+    X(8, false, false, false, kPmStormSend) X(4, false, false, false, kPmStormSend)
 
 struct ProgressRow { int w; bool bulk, ll, ph; uint32_t pm; void (*kernel)(rlo::Params); };
 #define X(W, B, L, H, PM) {W, B, L, H, rlo::PM, rlo::rlo_progress_kernel<W, B, L, H, rlo::PM>},
@@ -3531,7 +3644,11 @@ extern "C" int rlo_pick_progress(int variant, uint32_t mode, int pend_hbm, uint3
                           : prog == rlo::MODE_STORM ? rlo::kPmStorm
                                                     : rlo::kPmAll;
     int row;
-    if ((mode & rlo::MODE_SENDB) && prog == 0u) {
+    if ((mode & rlo::MODE_SENDS) && prog == 0u) {
+        // the storm send program (the launch adds MODE_STORM for the kernel): the storm-send instantiation of the
+        // world's variant, without doorbells, or nothing (a bulk world has the bulk send program)
+        row = !bulk && !ll ? progress_row(w, false, false, false, rlo::kPmStormSend) : -1;
+    } else if ((mode & rlo::MODE_SENDB) && prog == 0u) {
         // the bulk send program (the launch adds MODE_LAT for the kernel): its own instantiation or nothing
         row = bulk && ll ? progress_row(4, true, true, false, rlo::kPmSendBulk) : -1;
     } else {

@@ -440,7 +440,7 @@ struct rlo_world {
     rlo::Params P{};
     DevBuf<int64_t> d_sched_off, d_expect_bcast, d_prop_off, d_expect_dec;
     DevBuf<uint32_t> d_sched_ids, d_prop_data_off, d_prop_data_len, d_isp_off, d_lat_count, d_lat_round;
-    DevBuf<uint32_t> d_lat_own_off, d_lat_own, d_send_own_len;
+    DevBuf<uint32_t> d_lat_own_off, d_lat_own, d_send_own_len, d_sched_len;
     DevBuf<int32_t> d_lat_origin, d_prop_pid;
     DevBuf<uint64_t> d_lat_out, d_lat_obs;
     uint32_t* d_xcd = nullptr;  // RLO_PART_ONE_XCD: the placement check word (uncached)
@@ -1646,6 +1646,65 @@ int rlo_program_send_bulk(rlo_world_t* w, const rlo_send_bulk_cfg_t* cfg) {
     return RLO_OK;
 }
 
+// the storm send program (rlo_hip.h rlo_send_storm_cfg_t): what can be refused without a GPU
+int rlo_send_storm_check(const rlo_send_storm_cfg_t* cfg, int n_ranks, uint32_t max_payload) {
+    if (!cfg || n_ranks < 1 || cfg->k < 1 || cfg->k > 0xFFFFFFFFll || !cfg->origin) return RLO_E_INVAL;
+    const uint32_t slot = cfg->slot;
+    const uint64_t cap = ((uint64_t)max_payload + 15u) & ~15ull;  // (what a ring slot of the world carries)
+    if (slot == 0 || (slot & 15u) || slot > cap || cap > 65520u) return RLO_E_INVAL;
+    if (!cfg->src || !cfg->dst || ((uintptr_t)cfg->src & 15u) || ((uintptr_t)cfg->dst & 15u)) return RLO_E_INVAL;
+    if (cfg->flags & ~(RLO_FLAG_LOG | RLO_FLAG_HIST | RLO_FLAG_PROF)) return RLO_E_INVAL;
+    for (int64_t i = 0; i < cfg->k; i++) {
+        if (cfg->origin[i] < 0 || cfg->origin[i] >= n_ranks) return RLO_E_INVAL;
+        if (cfg->len && (cfg->len[i] == 0 || cfg->len[i] > slot)) return RLO_E_INVAL;
+    }
+    if (cfg->rank_stride) {  // a rank's places must hold its last message
+        const uint64_t last = cfg->len ? ((uint64_t)cfg->len[cfg->k - 1] + 15u) & ~15ull : slot;
+        if ((cfg->rank_stride & 15u) || cfg->rank_stride < (uint64_t)(cfg->k - 1) * slot + last) return RLO_E_INVAL;
+    }
+    return RLO_OK;
+}
+
+int rlo_program_send_storm(rlo_world_t* w, const rlo_send_storm_cfg_t* cfg) {
+    if (!w || !cfg) return RLO_E_INVAL;
+    // (a world with bulk messages has rlo_program_send_bulk; RLO_PART_ONE_XCD worlds run the hop kernel or nothing)
+    if (w->L.bulk_max || w->d_xcd) return RLO_E_INVAL;
+    int rc = rlo_send_storm_check(cfg, w->L.n, w->max_payload);
+    if (rc) return rc;
+    if (!w->connected) return RLO_E_NOTCONNECTED;
+    base_params(w);
+    rlo::Params& P = w->P;
+    // per local rank the messages it originates, ascending, and their lengths beside them (the storm's own lists)
+    std::vector<uint32_t> own_len;
+    const auto own = own_lists<int64_t>(w, cfg->k, [&](int64_t i) { return cfg->origin[i]; });
+    own_len.assign(own.idx.size(), 0);
+    for (size_t at = 0; at < (size_t)own.off[w->nl]; at++) own_len[at] = cfg->len ? cfg->len[own.idx[at]] : cfg->slot;
+    if (w->d_sched_off.upload(own.off) || w->d_sched_ids.upload(own.idx) || w->d_sched_len.upload(own_len) ||
+        w->d_expect_bcast.upload(own.expect))
+        return RLO_E_HIP;
+    // (the launch adds MODE_STORM for the kernel -- the program is the storm's open loop -- but the pick sees
+    // MODE_SENDS alone: rlo_pick_progress.  No doorbells: the storm never runs with them)
+    P.mode = rlo::MODE_SENDS | flag_modes(cfg->flags);
+    P.len = cfg->slot;
+    P.len_lo = P.len_hi = cfg->slot;
+    P.window = std::min<uint32_t>(cfg->window ? cfg->window : 64, 64u);  // one wave prefetches the ids and lengths
+    P.sched_off = w->d_sched_off.p;
+    P.sched_ids = w->d_sched_ids.p;
+    P.sched_len = w->d_sched_len.p;
+    P.expect_bcast = w->d_expect_bcast.p;
+    P.send_src = static_cast<const uint8_t*>(cfg->src);
+    P.send_dst = static_cast<uint8_t*>(cfg->dst);
+    P.send_k = (uint32_t)cfg->k;
+    P.send_slot = cfg->slot;
+    P.send_rank_stride = cfg->rank_stride ? cfg->rank_stride : (uint64_t)cfg->k * cfg->slot;
+    w->lat_rounds = 0;
+    w->tl_rows = 0;
+    rc = setup_log(w, cfg->flags, cfg->log_cap, false);  // records only: dst is the payload
+    if (rc) return rc;
+    w->have_program = true;
+    return RLO_OK;
+}
+
 // the device judge registry (rlo_kernel.hip judge_eval) and its per-rank tables, for every world
 // rank (a part uses its own ranks' entries)
 static int set_judge(rlo_world* w, const rlo_iar_cfg_t* cfg) {
@@ -2189,6 +2248,8 @@ int rlo_launch_ex(rlo_world_t* w, void* stream, uint32_t flags) {
     // MODE_LAT set, the world keeps MODE_SENDB alone (what picks the kernel, rlo_pick_progress)
     rlo::Params PK = w->P;
     if (PK.mode & rlo::MODE_SENDB) PK.mode |= rlo::MODE_LAT;
+    // ... and the storm send program the storm's open loop: MODE_STORM for its kernel, MODE_SENDS alone in the world
+    if ((PK.mode & rlo::MODE_SENDS) && !(PK.mode & (rlo::MODE_LAT | rlo::MODE_IAR | rlo::MODE_HOST))) PK.mode |= rlo::MODE_STORM;
     const hipError_t e = plan.hop ? rlo_launch_hop(plan.row, &PK, plan.blocks, plan.dyn_lds, s)
                                   : rlo_launch_progress(plan.row, &PK, plan.blocks, plan.dyn_lds, s);
     if (e != hipSuccess) { g_last_hip = (int)e; return RLO_E_HIP; }

@@ -13,7 +13,9 @@ rank 0's clock at each round's completion) or
 part creates its own device buffers (dst pre-filled with `fill`, 0xA5), and st["dst"] is the world's destination
 bytes as a NumPy array [rank][message][slot]; or
 {"kind": "send_bulk", "origins", "stride", "src": the source bytes (NumPy, message i at i * stride), "lens", "log",
-"fill"} (worlds with bulk messages): likewise, st["dst"] [rank][message][stride].
+"fill"} (worlds with bulk messages): likewise, st["dst"] [rank][message][stride]; or
+{"kind": "send_storm", "origins", "slot", "src", "lens", "window", "log", "fill"} (run_inprocess only): the storm send
+program, buffers and st["dst"] as for "send".
 """
 import ctypes
 import multiprocessing as mp
@@ -105,6 +107,17 @@ def _program(w, spec):
         w._send_bufs = (src, dst)
         w.program_send(spec["origins"], src, dst, slot, lens=spec.get("lens"), ordered=spec.get("ordered", False),
                        log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False))
+    elif spec["kind"] == "send_storm":  # buffers as for "send" (parts of one process)
+        import torch
+
+        dev = torch.device("cuda", w.device if w.device >= 0 else torch.cuda.current_device())
+        k, slot = len(spec["origins"]), spec["slot"]
+        src = torch.from_numpy(np.ascontiguousarray(spec["src"], dtype=np.uint8).reshape(-1)).to(dev)
+        dst = torch.full((w.n_local * k * slot,), spec.get("fill", 0xA5), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        w._send_bufs = (src, dst)
+        w.program_send_storm(spec["origins"], src, dst, slot, lens=spec.get("lens"), window=spec.get("window", 64),
+                             log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False))
     elif spec["kind"] == "send_bulk":
         # the part's own device buffers, as for "send", but allocated through the HIP runtime the engine itself uses: a
         # spawned part process has no other (torch found no GPU there once the engine's runtime was up)
@@ -120,12 +133,12 @@ def _program(w, spec):
 
 def _collect(w, spec):
     st = w.stats()
-    if spec["kind"] in ("send", "send_bulk"):
+    if spec["kind"] in ("send", "send_bulk", "send_storm"):
         w.info_now()  # (last_kernel: the kernel this launch ran)
     out = {"rank_begin": w.rank_begin, "stats": st, "ms": w.kernel_ms(), "info": dict(w.info)}
     if spec["kind"] == "lat" and w.rank_begin == 0:
         out["rounds"] = w.round_ticks()
-    if spec["kind"] == "send":  # this part's destination buffer: [local rank][message][slot] bytes
+    if spec["kind"] in ("send", "send_storm"):  # this part's destination buffer: [local rank][message][slot] bytes
         out["dst"] = w._send_bufs[1].cpu().numpy().reshape(w.n_local, len(spec["origins"]), spec["slot"])
     if spec["kind"] == "send_bulk":
         out["dst"] = w._send_bufs[1].download().reshape(w.n_local, len(spec["origins"]), spec["stride"])

@@ -13,6 +13,8 @@ Programs map the reference's application loops onto the device:
   send_bulk() -- the same for large buffers in a world with bulk messages: closed-loop bulk bcasts read from and
                 written to the caller's device buffers by the mover workgroups (program_send_bulk; bcast_tensor of a
                 bulk world)
+  send_storm() -- the same at storm rate: open-loop bcasts from any ranks in any mix on the progress kernel, small
+                and medium messages up to max_payload (program_send_storm; bcast_rows)
 """
 import ctypes
 
@@ -247,6 +249,83 @@ class World:
         check(self.lib.rlo_program_send_bulk(self.h, ctypes.byref(cfg)), "rlo_program_send_bulk")
         self._lat_rounds = k
 
+    def program_send_storm(self, origins, src, dst, slot, lens=None, rank_stride=0, window=64, log=False, hist=False,
+                           log_cap=0, prof=False):
+        """rlo_program_send_storm (worlds without bulk messages): message i (len(origins) of them, open loop, per-origin
+        FIFO) is a bcast from rank origins[i] of the lens[i] (None: slot) bytes at src + i * slot, DEVICE memory; local
+        rank lr's copy lands at dst + lr * rank_stride + i * slot (rank_stride 0: k * slot), DEVICE memory.  slot: a
+        multiple of 16, at most the world's max_payload.  src / dst as for program_send, 16-B aligned; src is read for
+        round16(lens[i]) bytes of each message.  The progress kernel's storm-send instantiation runs it."""
+        origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
+        k = int(origin.size)
+        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
+        if ln is not None and ln.size != k:
+            raise ValueError("program_send_storm: %d lengths for %d messages" % (ln.size, k))
+        sp, sn = _dev_extent(src)
+        dp, dn = _dev_extent(dst)
+        if k and slot > 0 and slot % 16 == 0 and rank_stride % 16 == 0:
+            # the buffers hold what the program reads and writes (the argument ranges themselves: rlo_send_storm_check)
+            last = -(-int(ln[-1] if ln is not None else slot) // 16) * 16
+            rs = rank_stride or k * slot
+            if sn < (k - 1) * slot + last or dn < (self.n_local - 1) * rs + (k - 1) * slot + last:
+                raise ValueError("program_send_storm: src holds %d bytes, dst %d: too small for %d messages of slot %d"
+                                 % (sn, dn, k, slot))
+        cfg = L.SendStormCfg()
+        cfg.k = k
+        cfg.origin = origin.ctypes.data
+        cfg.len = None if ln is None else ln.ctypes.data
+        cfg.src, cfg.dst = sp, dp
+        cfg.slot, cfg.window, cfg.rank_stride = slot, window, rank_stride
+        cfg.flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0) | (L.RLO_FLAG_PROF if prof else 0)
+        cfg.log_cap = log_cap
+        self._keep = [origin, ln, src, dst, cfg]
+        check(self.lib.rlo_program_send_storm(self.h, ctypes.byref(cfg)), "rlo_program_send_storm")
+        self._lat_rounds = 0
+
+    def bcast_rows(self, origins, t, stream=None):
+        """Broadcast every row of the contiguous CUDA tensor t of shape [k, ...]: row i (at most max_payload bytes)
+        from rank origins[i] of a one-part world without bulk messages, all k in ONE storm-send launch on torch's
+        current stream (or `stream`, a raw hipStream_t).  Returns a tensor of shape [n, k, ...] and t's dtype: [r, i]
+        is rank r's copy of row i (an origin's own rows are copied in from t here).  A row that is no multiple of 16
+        bytes goes through a padded staging copy: t is never read past its end.
+        Which call suits which shape: many rows from many origins -- this one, the progress kernel's batched storm
+        path, whose rate grows with the world; one tensor from one origin, or a few messages in a small world where
+        each one's latency counts -- bcast_tensor (the hop kernel's send program, one message per rank-wave at a
+        time); rows beyond max_payload -- a world with bulk messages and bcast_tensor."""
+        import torch
+
+        if self.n_local != self.n:
+            raise ValueError("bcast_rows: one-part worlds only")
+        if self.info["bulk_max"]:
+            raise ValueError("bcast_rows: a world without bulk messages")
+        if not (t.is_cuda and t.is_contiguous()) or t.dim() < 1:
+            raise ValueError("bcast_rows: a contiguous tensor [k, ...] in device memory")
+        origin = np.asarray(origins, dtype=np.int64).reshape(-1)
+        k, n = int(t.shape[0]), self.n
+        if origin.size != k or (k and (origin.min() < 0 or origin.max() >= n)):
+            raise ValueError("bcast_rows: one origin in [0, %d) per row" % n)
+        row = t[0].numel() * t.element_size() if k else 0
+        if k == 0 or row == 0:
+            return t.unsqueeze(0).repeat((n,) + (1,) * t.dim())
+        slot = rows_slot(row, self.info["slot_stride"] - 16)
+        flat = t.reshape(k, -1).view(torch.uint8)
+        if slot == row and flat.data_ptr() % 16 == 0:
+            src = flat
+        else:  # a padded staging copy: t is never read past its end
+            src = torch.zeros((k, slot), dtype=torch.uint8, device=t.device)
+            src[:, :row].copy_(flat)
+        dst = torch.empty((n, k, slot), dtype=torch.uint8, device=t.device)
+        self.program_send_storm(origin, src, dst, slot, lens=None if slot == row else [row] * k)
+        if stream is None:
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+        self.launch(stream=stream)
+        self.wait()
+        out = dst[:, :, :row].contiguous().view(t.dtype).reshape((n,) + tuple(t.shape))
+        idx = torch.as_tensor(origin, device=t.device)
+        ar = torch.arange(k, device=t.device)
+        out[idx, ar] = t
+        return out
+
     def _bcast_tensor_bulk(self, origin, t, stream):
         """bcast_tensor in a world with bulk messages: the bulk send program, fragments of at most bulk_max"""
         import torch
@@ -412,6 +491,20 @@ def send_fragments(nbytes, slot=1008):
     return [(off, min(slot, nbytes - off)) for off in range(0, max(int(nbytes), 0), slot)]
 
 
+def rows_slot(row_bytes, max_payload):
+    """the message place World.bcast_rows gives a row of row_bytes bytes: the row rounded up to 16 bytes (a row that
+    is no multiple of 16 is padded in a staging copy); a row beyond the world's max_payload is refused.  Pure
+    Python, no GPU"""
+    row_bytes, cap = int(row_bytes), -(-int(max_payload) // 16) * 16
+    if row_bytes <= 0:
+        raise ValueError("rows_slot: an empty row")
+    if row_bytes > int(max_payload):
+        raise ValueError("rows_slot: a row of %d bytes in a world of max_payload %d" % (row_bytes, max_payload))
+    slot = -(-row_bytes // 16) * 16
+    assert slot <= cap
+    return slot
+
+
 def bulk_fragments(nbytes, bulk_max):
     """the (offset, len) fragments that cover nbytes as bulk messages of a world with this bulk_max, in order: each at
     most bulk_max rounded down to 16 bytes, every one but the last that long (a multiple of 16, so every fragment
@@ -437,6 +530,24 @@ def send_bulk_check(origins, stride, n_ranks, bulk_max, lens=None, rank_stride=0
     cfg.stride, cfg.rank_stride = stride, rank_stride
     cfg.flags = flags
     return L.load().rlo_send_bulk_check(ctypes.byref(cfg), n_ranks, bulk_max)
+
+
+def send_storm_check(origins, slot, n_ranks, max_payload, lens=None, rank_stride=0, window=0, src=0x1000, dst=0x1000,
+                     flags=0):
+    """rlo_send_storm_check: the argument checks of the storm send program that need no GPU; returns RLO_OK or
+    RLO_E_INVAL (src / dst: pointers as integers, never dereferenced)"""
+    origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
+    ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
+    if ln is not None and ln.size != origin.size:
+        raise ValueError("send_storm_check: %d lengths for %d messages" % (ln.size, origin.size))
+    cfg = L.SendStormCfg()
+    cfg.k = int(origin.size)
+    cfg.origin = origin.ctypes.data if origin.size else None
+    cfg.len = None if ln is None or not ln.size else ln.ctypes.data
+    cfg.src, cfg.dst = src, dst
+    cfg.slot, cfg.window, cfg.rank_stride = slot, window, rank_stride
+    cfg.flags = flags
+    return L.load().rlo_send_storm_check(ctypes.byref(cfg), n_ranks, max_payload)
 
 
 def pool_trim(what):

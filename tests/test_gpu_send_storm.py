@@ -1,0 +1,300 @@
+"""GPU tests of the storm send program (rlo_program_send_storm): open-loop rootless bcasts from any ranks in any mix
+whose payloads are read from a caller-owned source buffer in device memory and written, at every receiver, to a
+caller-owned destination buffer in device memory -- on the progress kernel's storm-send instantiations (8 waves: the
+small copy path with the forwarding tables; 4 waves: the small and the large path), in one part and two, and through
+World.bcast_rows.
+
+Expected values never come from the engine: payload bytes are this file's seeded NumPy source, tree parents
+pyoracle.tree, checksums pyoracle.msg_checksum summed over what a rank must receive, counts k minus the rank's own.
+dst is pre-filled with 0xA5, so the bytes that must stay unwritten are checked too."""
+import re
+
+import numpy as np
+import pytest
+
+import pyoracle as orc
+
+pytestmark = pytest.mark.gpu
+FILL = 0xA5
+TAG_BCAST = 0
+MASK64 = (1 << 64) - 1
+
+
+@pytest.fixture(scope="module")
+def rlo():
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import rlo as _rlo
+
+    return _rlo
+
+
+def _gen(n, slot, k, seed, origins=None):
+    """a seeded workload: origins (all ranks, a random mix), lengths from {1, 15, 16, 17, slot - 1, slot} -- large
+    slots add {64, 65, 368, 369, 1008, 1024, 1025}: the staged 5 chunks, the small copy path's 24 chunks, the hop
+    kernel's limit -- within [1, slot], and k x slot source bytes"""
+    rng = np.random.default_rng(seed)
+    if origins is None:
+        origins = rng.integers(0, n, k)
+    origins = np.asarray(origins, dtype=np.int32)
+    pool = {1, 15, 16, 17, slot - 1, slot}
+    if slot > 112:
+        pool |= {64, 65, 368, 369, 1008, 1024, 1025}
+    choices = sorted(x for x in pool if 1 <= x <= slot)
+    lens = rng.choice(choices, len(origins)).astype(np.uint32)
+    lens[:len(choices)] = choices[:len(origins)]  # every boundary at least once
+    src = rng.integers(0, 256, (len(origins), slot), dtype=np.uint8)
+    return origins, lens, src
+
+
+def _expected(n, origins, lens, src):
+    """(dst bytes [n][k][slot], deliveries [n], originated [n], checksum [n]) a correct run leaves"""
+    k, slot = src.shape
+    col = np.arange(slot)[None, :]
+    ln = lens.astype(np.int64)[:, None]
+    msg = np.where(col < ln, src, np.where(col < (ln + 15) // 16 * 16, 0, FILL)).astype(np.uint8)
+    want = np.broadcast_to(msg, (n, k, slot)).copy()
+    want[origins, np.arange(k)] = FILL  # the origin's own place is not written
+    cs = [orc.msg_checksum(int(origins[i]), i, TAG_BCAST, bytes(src[i, :lens[i]])) for i in range(k)]
+    total = sum(cs) & MASK64
+    own_sum = [0] * n
+    for i in range(k):
+        own_sum[origins[i]] += cs[i]
+    sums = np.array([(total - own_sum[r]) & MASK64 for r in range(n)], dtype=np.uint64)
+    own = np.bincount(origins, minlength=n)
+    return want, k - own, own, sums
+
+
+def _check(st, got, n, origins, lens, src):
+    want, cnt, own, sums = _expected(n, origins, lens, src)
+    assert (st["error"] == 0).all(), (st["error"], st["error_aux"])
+    assert np.array_equal(st["bcast_delivered"].astype(np.int64), cnt)
+    assert np.array_equal(st["originated"].astype(np.int64), own)
+    if not np.array_equal(got, want):
+        r, i, b = (int(x[0]) for x in np.nonzero(got != want))
+        raise AssertionError("rank %d message %d (origin %d, len %d) byte %d: got 0x%02x, want 0x%02x; %d bytes differ" %
+                             (r, i, origins[i], lens[i], b, got[r, i, b], want[r, i, b], int((got != want).sum())))
+    assert np.array_equal(st["bcast_sum"], sums)
+
+
+def _launch(w, origins, lens, src, rank_stride=0, **kw):
+    """one launch on device buffers made here (dst pre-filled with 0xA5): the progress kernel ran, no rank erred;
+    returns (stats, dst bytes [n_local][rank_stride or k * slot])"""
+    import torch
+
+    k, slot = src.shape
+    rs = rank_stride or k * slot
+    s = torch.from_numpy(src.reshape(-1)).cuda()
+    d = torch.full((w.n_local * rs,), FILL, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    w.program_send_storm(origins, s, d, slot, lens=lens, rank_stride=rank_stride, **kw)
+    w.run()
+    assert w.info_now()["last_kernel"] == 0
+    st = w.stats()
+    assert (st["error"] == 0).all(), (st["error"], st["error_aux"])
+    return st, d.cpu().numpy().reshape(w.n_local, rs)
+
+
+# (n, max_payload, k, waves): 8 waves -- slots the small copy path stages whole, the forwarding tables (256: a CU per
+# rank; 300: two rank-workgroups per CU); 4 waves -- 368: the small path's longest slot; 4096 / 32768: the large path
+CASES = [(4, 112, 256, 8), (13, 112, 832, 8), (64, 64, 4096, 8), (256, 64, 4096, 8), (8, 368, 512, 4), (17, 368, 544, 4),
+         (300, 64, 1200, 4), (8, 4096, 96, 4), (13, 4096, 104, 4), (4, 32768, 16, 4)]
+
+
+@pytest.mark.parametrize("n,mp,k,waves", CASES, ids=lambda v: str(v))
+def test_exact_bytes(rlo, n, mp, k, waves):
+    origins, lens, src = _gen(n, mp, k, 1000 + n + mp)
+    try:
+        w = rlo.World(n, max_payload=mp)
+    except rlo.RloError as e:
+        if n == 300 and "[-3]" in str(e):  # RLO_E_OCCUPANCY
+            pytest.skip("300 rank-workgroups are not co-resident on this device: the world was refused")
+        raise
+    with w:
+        assert w.info["waves"] == waves
+        try:
+            st, got = _launch(w, origins, lens, src)
+        except rlo.RloError as e:
+            if n == 300 and str(e).startswith("rlo_run failed") and "[-1]" in str(e):  # (RLO_E_INVAL from the launch itself)
+                pytest.skip("300 rank-workgroups are not co-resident on this device: the launch was refused")
+            raise
+        _check(st, got.reshape(n, k, mp), n, origins, lens, src)
+        if mp >= 4096:
+            assert w.info["pull"] == 1  # pulled payloads: the default of large-slot worlds
+
+
+@pytest.mark.parametrize("org", [[0], [1, 5]], ids=["one", "opposite"])
+def test_ring_wrap_and_refused_admissions(rlo, org):
+    """the smallest rings a world takes, every originator sending 8 x the ring capacity: tails wrap, originations
+    are refused and retried"""
+    n, slot, cap = 8, 112, 16
+    origins = [org[i % len(org)] for i in range(8 * cap * len(org))]
+    origins, lens, src = _gen(n, slot, len(origins), 3000 + len(org), origins=origins)
+    assert np.bincount(origins, minlength=n)[org].min() >= 8 * cap
+    with rlo.World(n, max_payload=slot, ring_slots=cap) as w:
+        assert w.info["ring_slots"] == cap
+        st, got = _launch(w, origins, lens, src)
+        _check(st, got.reshape(n, len(origins), slot), n, origins, lens, src)
+
+
+@pytest.mark.parametrize("n,mp", [(8, 64), (13, 64), (64, 64), (8, 4096)], ids=lambda v: str(v))
+def test_trees_and_per_origin_fifo(rlo, n, mp):
+    k = 12 * n
+    origins, lens, src = _gen(n, mp, k, 2000 + n + mp)
+    parent = {o: orc.tree(n, o)[0] for o in range(n)}
+    with rlo.World(n, max_payload=mp) as w:
+        st, got = _launch(w, origins, lens, src, log=True, log_cap=k)
+        _check(st, got.reshape(n, k, mp), n, origins, lens, src)
+        for r in range(n):
+            rows = w.log(r, cap=k)
+            assert len(rows) == k - int((origins == r).sum())
+            last = {}
+            for kind, tag, origin, frm, ident, ln, _vote, _aux, pidx in rows:
+                assert (kind, tag) == (1, TAG_BCAST) and pidx == 0xFFFFFFFF  # a delivery record, no payload copy
+                assert origin == origins[ident] != r and ln == lens[ident]
+                assert frm == parent[origin][r], (r, origin, ident, frm)
+                assert ident > last.get(origin, -1), (r, origin, ident)  # per-origin FIFO
+                last[origin] = ident
+
+
+def test_pushed_large_payloads(rlo, monkeypatch):
+    """RLO_PULL=0 (read when the world is created): large messages travel whole through the rings"""
+    monkeypatch.setenv("RLO_PULL", "0")
+    n, mp, k = 8, 4096, 96
+    origins, lens, src = _gen(n, mp, k, 1500)
+    with rlo.World(n, max_payload=mp) as w:
+        assert w.info["pull"] == 0
+        st, got = _launch(w, origins, lens, src)
+        _check(st, got.reshape(n, k, mp), n, origins, lens, src)
+
+
+def test_three_launches_then_other_programs(rlo):
+    """different seeds, origins, lengths, k and buffers every time, then the storm and the send program on the same
+    world: no stale schedule, length or pointer state"""
+    n, slot = 8, 112
+    with rlo.World(n, max_payload=slot) as w:
+        for j, k in enumerate((40, 96, 24)):
+            origins, lens, src = _gen(n, slot, k, 5000 + j)
+            st, got = _launch(w, origins, lens, src)
+            _check(st, got.reshape(n, k, slot), n, origins, lens, src)
+        ks, ln, seed = 128, 64, 11
+        w.program_storm(ks, ln, seed=seed)
+        w.run()
+        st = w.stats()
+        ref = orc.storm(n, seed, ks, ln)
+        assert (st["error"] == 0).all()
+        assert np.array_equal(st["bcast_delivered"].astype(np.int64), ref["count"])
+        assert np.array_equal(st["bcast_sum"], ref["sum"])
+        import torch
+
+        k = 32
+        origins, lens, src = _gen(n, slot, k, 5100)
+        s = torch.from_numpy(src.reshape(-1)).cuda()
+        d = torch.full((n * k * slot,), FILL, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        w.program_send(origins, s, d, slot, lens=lens)
+        w.run()
+        assert w.info_now()["last_kernel"] == 1
+        _check(w.stats(), d.cpu().numpy().reshape(n, k, slot), n, origins, lens, src)
+
+
+def test_rank_stride_gap_stays_unwritten(rlo):
+    n, slot, k = 8, 112, 64
+    origins, lens, src = _gen(n, slot, k, 6500)
+    rs = k * slot + 256
+    with rlo.World(n, max_payload=slot) as w:
+        st, got = _launch(w, origins, lens, src, rank_stride=rs)
+        assert (got[:, k * slot:] == FILL).all()  # the gap up to rank_stride
+        _check(st, got[:, :k * slot].reshape(n, k, slot), n, origins, lens, src)
+
+
+def _forge_bus(blob):
+    m = re.search(rb"[0-9a-fA-F]{4}:[0-9a-fA-F]{2}:[0-9a-fA-F]{2}\.[0-9]", blob)
+    assert m, "no PCI bus id in the exported blob"
+    return blob[:m.start()] + b"ffff:ff:1f.7" + blob[m.end():]
+
+
+@pytest.mark.parametrize("forged", [False, True], ids=["agent", "system"])
+def test_parts(rlo, forged):
+    """two parts in one process, each with its own src and dst; forged: every part sees its peer "on another GPU", so
+    both store at system scope"""
+    from rlo import sharded
+
+    n, bounds, slot = 8, [0, 3, 8], 64
+    k = 16 * n
+    origins, lens, src = _gen(n, slot, k, 6000 + n)
+
+    def forge(p, blobs):
+        return [b if q == p else _forge_bus(b) for q, b in enumerate(blobs)]
+
+    spec = {"kind": "send_storm", "origins": origins, "lens": lens, "slot": slot, "src": src}
+    (st, _, _), rcs = sharded.run_inprocess(n, bounds, spec, max_payload=slot, uncached=forged,
+                                            blobs_for=forge if forged else None)
+    assert rcs == [0, 0], (st["error"], st["error_aux"])
+    assert (st["part_last_kernel"] == 0).all()
+    assert (st["part_sys_scope"] == (1 if forged else 0)).all()
+    _check(st, st["dst"], n, origins, lens, src)
+
+
+def _latency_runs_clean(w):
+    w.program_latency(16, 64)
+    w.run()
+    st = w.stats()
+    assert (st["error"] == 0).all() and int(st["originated"].sum()) == 16
+
+
+def test_refusals(rlo):
+    import torch
+
+    n, slot, k = 8, 64, 16
+    origins, lens, src = _gen(n, slot, k, 7000)
+    s = torch.from_numpy(src.reshape(-1)).cuda()
+    d = torch.full((n * k * 128,), FILL, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    inval = r"rlo_program_send_storm failed.*\[-1\]"  # RLO_E_INVAL from the program call, before anything is uploaded
+    with rlo.World(n, max_payload=slot, bulk_max=1 << 20) as w:  # a bulk world
+        _latency_runs_clean(w)
+        with pytest.raises(rlo.RloError, match=inval):
+            w.program_send_storm(origins, s, d, slot, lens=lens)
+        w.run()  # the previous program still runs
+        assert (w.stats()["error"] == 0).all() and int(w.stats()["originated"].sum()) == 16
+    with rlo.World(n, max_payload=slot, one_xcd=True) as w:  # a one-XCD world
+        _latency_runs_clean(w)
+        with pytest.raises(rlo.RloError, match=inval):
+            w.program_send_storm(origins, s, d, slot, lens=lens)
+        w.run()
+        assert (w.stats()["error"] == 0).all() and int(w.stats()["originated"].sum()) == 16
+    with rlo.World(n, max_payload=slot) as w:  # a slot beyond max_payload
+        _latency_runs_clean(w)
+        with pytest.raises(rlo.RloError, match=inval):
+            w.program_send_storm(origins, torch.cat([s, s]), d, 128)
+        w.run()
+        assert (w.stats()["error"] == 0).all() and int(w.stats()["originated"].sum()) == 16
+        with pytest.raises(ValueError):  # extents are checked before the library sees them
+            w.program_send_storm(origins, s[:-16], d, slot)
+        with pytest.raises(ValueError):
+            w.program_send_storm(origins, s, d[:n * k * slot - 16], slot)
+    torch.cuda.synchronize()
+    assert bool((d == FILL).all())  # no refused program wrote anything
+
+
+@pytest.mark.parametrize("dtype,shape,n,mp", [("float32", (96, 24), 8, 4096), ("uint8", (40, 1000), 8, 1008),
+                                               ("bfloat16", (12, 2048), 4, 4096)], ids=lambda v: str(v))
+def test_bcast_rows(rlo, dtype, shape, n, mp):
+    """the tensor is produced by a torch kernel on the current stream right before the call, no synchronise"""
+    import torch
+
+    rng = np.random.default_rng(8000 + shape[0])
+    origins = rng.integers(0, n, shape[0])
+    with rlo.World(n, max_payload=mp) as w:
+        base = torch.arange(shape[0] * shape[1], device="cuda", dtype=torch.float32).reshape(shape)
+        t = ((base * 0.37 - 11.0) % 251).to(getattr(torch, dtype))
+        keep = t.clone()
+        out = w.bcast_rows(origins, t)
+        assert w.info_now()["last_kernel"] == 0
+        assert out.shape == (n,) + tuple(t.shape) and out.dtype == t.dtype
+        assert torch.equal(t, keep)  # t itself is unchanged
+        for r in range(n):
+            assert torch.equal(out[r], t), r
