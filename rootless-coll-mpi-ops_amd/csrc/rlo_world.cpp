@@ -1747,13 +1747,13 @@ int rlo_program_iar(rlo_world_t* w, const rlo_iar_cfg_t* cfg, int64_t nprop, con
     if (!w->connected) return RLO_E_NOTCONNECTED;
     const uint32_t pool = cfg->pool ? cfg->pool : 1u;
     if (pool > w->L.pend_slots) return RLO_E_INVAL;  // the world's proposal_pool bounds it
-    base_params(w);
-    rlo::Params& P = w->P;
-    P.own_pool = pool;
-    for (int64_t i = 0; i < nprop; i++) {
+    for (int64_t i = 0; i < nprop; i++) {  // (refused before the program loaded earlier is touched: it still runs)
         if (origin[i] < 0 || origin[i] >= w->L.n) return RLO_E_INVAL;
         if (16ull + data_len[i] > w->max_payload) return RLO_E_INVAL;
     }
+    base_params(w);
+    rlo::Params& P = w->P;
+    P.own_pool = pool;
     // per local rank its proposals, in order: pid, data offset and length by place; the data in the caller's order
     const size_t most = (size_t)std::max<int64_t>(nprop, 1);
     std::vector<int32_t> ppid(most);

@@ -133,8 +133,7 @@ def _program(w, spec):
 
 def _collect(w, spec):
     st = w.stats()
-    if spec["kind"] in ("send", "send_bulk", "send_storm"):
-        w.info_now()  # (last_kernel: the kernel this launch ran)
+    w.info_now()  # (last_kernel: the kernel this launch ran)
     out = {"rank_begin": w.rank_begin, "stats": st, "ms": w.kernel_ms(), "info": dict(w.info)}
     if spec["kind"] == "lat" and w.rank_begin == 0:
         out["rounds"] = w.round_ticks()
@@ -157,11 +156,11 @@ def merge(results):
     for key in results[0]["stats"]:
         st[key] = np.concatenate([r["stats"][key] for r in results])
     # per world rank: its part's rlo_world_info_t.peers / sys_scope (where that part's peers are)
-    for key in ("peers", "sys_scope"):
+    # (and last_kernel: the kernel its launch ran)
+    for key in ("peers", "sys_scope", "last_kernel"):
         st["part_" + key] = np.concatenate([np.full(len(r["stats"]["error"]), r["info"][key]) for r in results])
-    if "dst" in results[0]:  # the send program: every part's destination buffer, by world rank, and the kernel it ran
+    if "dst" in results[0]:  # the send program: every part's destination buffer, by world rank
         st["dst"] = np.concatenate([r["dst"] for r in results])
-        st["part_last_kernel"] = np.concatenate([np.full(len(r["stats"]["error"]), r["info"]["last_kernel"]) for r in results])
     logs = {}
     for r in results:
         logs.update(r.get("logs", {}))

@@ -13,6 +13,7 @@ import time
 import numpy as np
 import pytest
 
+import iar_payload_cases as pc
 import pyoracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -70,11 +71,22 @@ def test_host_bcast_matches_oracle(rlo, n, k, ln, maxp):
     assert (st["originated"] == k).all()
 
 
-def _run_iar(rlo, n, proposals, decline, pool=1, pend_hbm=False):
+def _first_diff(a, b):
+    """(lengths, first differing index) of two byte strings, for an assertion's message"""
+    return len(a), len(b), next((i for i in range(min(len(a), len(b))) if a[i] != b[i]), None)
+
+
+def _run_iar(rlo, n, proposals, decline, pool=1, pend_hbm=False, max_payload=256):
     """proposals: (origin, pid, data); at most `pool` per origin (pool 1: one own proposal per engine,
     rootless_ops.c:241; more: the proposal pool, :30 -- all submitted at once, the kernel keeps up
-    to `pool` in flight and holds the rest in the command ring)."""
+    to `pool` in flight and holds the rest in the command ring).  decline: per rank, or a function
+    (rank, origin, pid) -> bool.  Every judge request must carry the submitted PBuf, byte for byte, and every
+    action finds the bytes its rank approved equal to the submitted ones."""
     from rlo import abi
+    from rlo.host import pbuf
+
+    sent = {(o, pid): bytes(data) for o, pid, data in proposals}
+    assert len(sent) == len(proposals)
 
     judge, actions, pickups, results = [], [], [], []
     approved = {}
@@ -84,8 +96,12 @@ def _run_iar(rlo, n, proposals, decline, pool=1, pend_hbm=False):
         hw = hw_ref[0]
         k = ev["kind"]
         if k == abi.RLO_EV_JUDGE:
+            want = sent[(ev["origin"], ev["id"])]
+            assert ev["len"] == 16 + len(want), (r, ev["origin"], ev["id"], ev["len"], len(want))
+            assert ev["payload"] == pbuf(ev["id"], 1, want), (r, ev["origin"], ev["id"], _first_diff(ev["payload"], pbuf(ev["id"], 1, want)))
             data = ev["payload"][16:]
-            v = 0 if decline[r] else 1
+            no = decline(r, ev["origin"], ev["id"]) if callable(decline) else decline[r]
+            v = 0 if no else 1
             judge.append((r, ev["id"], 0, v, ev["origin"]))
             if v:
                 approved[(r, ev["origin"], ev["id"])] = data
@@ -95,6 +111,7 @@ def _run_iar(rlo, n, proposals, decline, pool=1, pend_hbm=False):
             hw.own_judge(r, ev, 1)
         elif k == abi.RLO_EV_ACTION:
             data = approved.pop((r, ev["origin"], ev["id"]))
+            assert data == sent[(ev["origin"], ev["id"])], (r, ev["origin"], ev["id"], _first_diff(data, sent[(ev["origin"], ev["id"])]))
             actions.append((r, ev["id"], 1, len(data), ev["origin"]))
         elif k == abi.RLO_EV_DELIVER_DECISION:
             pickups.append((r, ev["id"], ev["vote"], ev["origin"], 7))
@@ -103,7 +120,7 @@ def _run_iar(rlo, n, proposals, decline, pool=1, pend_hbm=False):
         else:
             raise AssertionError(ev)
 
-    with rlo.HostWorld(n, max_payload=256, pool=pool, pend_hbm=pend_hbm) as hw:
+    with rlo.HostWorld(n, max_payload=max_payload, pool=pool, pend_hbm=pend_hbm) as hw:
         assert hw.world.info["pend_hbm"] == (1 if pend_hbm else hw.world.info["pend_hbm"])
         hw_ref.append(hw)
         for o, pid, data in proposals:
@@ -141,6 +158,29 @@ def test_host_iar_matches_oracle(rlo, n, origins, mask_ranks, per, pool, pend_hb
     assert sorted(actions) == want_a
     assert sorted(pickups) == want_p
     assert sorted(results) == want_r
+
+
+@pytest.mark.parametrize("n,maxp,lens,pool,pend_hbm,seed", pc.HOST_CASES,
+                         ids=["n%d-%d-pool%d%s" % (c[0], c[1], c[3], "-pend-hbm" if c[4] else "") for c in pc.HOST_CASES])
+def test_host_iar_payloads_match_oracle(rlo, n, maxp, lens, pool, pend_hbm, seed):
+    """proposals of 0 bytes up to a full slot, seeded data over all byte values, every rank submitting one of each
+    length: beyond kLLCmdSlot a command takes the command ring instead of the command doorbell, beyond kBellChunks
+    chunks a message the ring alone, beyond the staged chunks the large-message rounds.  The judge is the seeded
+    hash judge, evaluated here in the callback, so about a quarter of the proposals is declined somewhere in the
+    tree; _run_iar compares every judge request's PBuf and every action's bytes with what was submitted"""
+    import iar_sets
+
+    props, cfg, keep, ppm = pc.host_case(n, lens, seed)
+    ev = iar_sets.oracle_events(n, props, cfg, pool)
+    iar_sets.input_conditions(props, ev)
+
+    def decline(r, origin, pid):
+        return orc.lib().orc_judge_hash(seed, r, pid) < ppm
+
+    judge, actions, pickups, results = _run_iar(rlo, n, props, decline, pool=pool, pend_hbm=pend_hbm, max_payload=maxp)
+    for kind, got in ((orc.ORC_EV_JUDGE, judge), (orc.ORC_EV_ACTION, actions), (orc.ORC_EV_PICKUP, pickups)):
+        assert sorted(got) == sorted((e[1], e[2], e[3], e[4], e[5]) for e in ev if e[0] == kind), kind
+    assert sorted(results) == sorted((e[1], e[2], e[3]) for e in ev if e[0] == orc.ORC_EV_RESULT)
 
 
 def test_host_relaunch_replays_nothing(rlo):
