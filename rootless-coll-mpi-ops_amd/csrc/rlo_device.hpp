@@ -81,6 +81,8 @@ enum Mode : uint32_t {
                             //   (kids_of / need_of) instead of reading its forwarding tables
     MODE_SENDS = 8388608u,  // the storm send program (the progress kernel's storm-send instantiations only): open-loop bcasts of
                             //   caller-owned device buffers at storm rate; the kernel runs it with MODE_STORM set too
+    MODE_NOPIPE = 16777216u,  // diagnostics build, A/B and test: the 8-wave storm kernel's iteration in its serial order (every
+                              //   wave copies, then wave 0 alone consumes, polls and selects) instead of the pipelined one
     MODE_CORRUPT = 65536u,  // diagnostics build, test of the VERIFY check: a direct scatter zeroes one granule of one copy
     MODE_HOST = 128u,  // host-service: originations / judge verdicts come from a host command ring,
                        //   deliveries / judge requests / results go to a host pickup ring (rootless_ops.h)

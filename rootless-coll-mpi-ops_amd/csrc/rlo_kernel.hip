@@ -963,6 +963,19 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
 #else
     [[maybe_unused]] const bool fwd_tab = kStorm8 && 4u * (uint32_t)P.n <= P.stage2_bytes;
 #endif
+    // kPipeC: the generated storm's 8-wave instantiation pipelines its iteration (ovl).  Wave 0's serial sections --
+    // consume of iteration i, the poll, the selection of iteration i + 1 -- need nothing of the small-message copy
+    // (G2), so wave 0 takes no copy items and runs them while waves 1-7 copy; ONE barrier (Y) stands behind both, where
+    // the serial order has the loop-top barrier and the "selection visible" one, and iteration i's counters are
+    // published behind it (every wave's stores drained before it: the hand-off rule as it was).  DESIGN.md 4 has the
+    // audit of the shared words.  Not the storm send program's: its selection writes lengths into stage slots the
+    // copy still reads.  The diagnostics build's RLO_NO_PIPELINE runs the serial order in the same binary
+    constexpr bool kPipeC = kStorm8 && PM == kPmStorm;
+#ifdef RLO_DIAG
+    [[maybe_unused]] const bool ovl = kPipeC && !(P.mode & MODE_NOPIPE);
+#else
+    constexpr bool ovl = kPipeC;
+#endif
 #define STG(c, q) (stage + (((uint32_t)(c) * nsmall + (uint32_t)(q)) << 4))
 #define OL(oi, r) olist[(uint32_t)(oi) * (uint32_t)kMaxCand + (uint32_t)(r)]
     // the pending entry of (origin, pool slot) (rlo_device.hpp Params.pend_slots)
@@ -2025,21 +2038,30 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 if (__builtin_amdgcn_readfirstlane((int)S.a_done) == (int)a_it) break;
             }
         }
-        VM_DRAIN();
-        BAR();  // every payload / vote store of the previous iteration has left its wave
+        // (wave 0) the previous iteration's counters, once every wave's stores of it have drained
+#define PUBLISH_PREV()                                                                                                \
+    do {                                                                                                              \
+        if (lane < nout && out_tail_r != PUB_OUT) { PUB_OUT = out_tail_r; pub64(OTPTR, out_tail_r, sys); }            \
+        if (lane < n_in2 && in_head_r != PUB_IN) { PUB_IN = in_head_r; pub64(IHPTR, in_head_r, sys); }                \
+        if (lane < sll && vin_head_r != PUB_VIN) { PUB_VIN = vin_head_r; pub64(VHPTR, vin_head_r, sys); }             \
+        if (lane < n_in) {                                                                                            \
+            const uint64_t vt = S.vout_tail[lane];                                                                    \
+            if (vt != PUB_VOUT) { PUB_VOUT = vt; pub64(VTPTR, vt, sys); }                                             \
+            S.vout_head[lane] = vout_head_r;                                                                          \
+        }                                                                                                             \
+        peer_failed = __builtin_amdgcn_readfirstlane(errf) != 0;                                                      \
+    } while (0)
+        if (!ovl) {
+            VM_DRAIN();
+            BAR();  // every payload / vote store of the previous iteration has left its wave
+        }
         PROF_STAMP(0);
 
         // ---------------- C (wave 0): publish the previous iteration, select this one
+        // (pipelined: the selection runs beside the other waves' copy of the previous iteration, whose counters are
+        // published behind barrier Y below)
         if (w == 0) {
-            if (lane < nout && out_tail_r != PUB_OUT) { PUB_OUT = out_tail_r; pub64(OTPTR, out_tail_r, sys); }
-            if (lane < n_in2 && in_head_r != PUB_IN) { PUB_IN = in_head_r; pub64(IHPTR, in_head_r, sys); }
-            if (lane < sll && vin_head_r != PUB_VIN) { PUB_VIN = vin_head_r; pub64(VHPTR, vin_head_r, sys); }
-            if (lane < n_in) {
-                const uint64_t vt = S.vout_tail[lane];
-                if (vt != PUB_VOUT) { PUB_VOUT = vt; pub64(VTPTR, vt, sys); }
-                S.vout_head[lane] = vout_head_r;
-            }
-            peer_failed = __builtin_amdgcn_readfirstlane(errf) != 0;
+            if (!ovl) PUBLISH_PREV();
             PSX(1);
             // pull worlds: relay slots whose references every child consumed are free again (the
             // records are in order; out_head_r = the children's consumption counts just polled)
@@ -2197,10 +2219,12 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
             rbase_r = base;
             rtake_r = take;
             noi_r = 0;
+            // (kPipeC: the copy of the previous iteration may still read out_tail0, n_oi and nchmax -- wave 0 writes
+            // them behind the barrier below, in either order of the iteration)
             if (lane < nout) {
-                S.out_tail0[lane] = out_tail_r;
+                if constexpr (!kPipeC) S.out_tail0[lane] = out_tail_r;
                 S.ofree[lane] = P.fwd_cap - (uint32_t)(out_tail_r - out_head_r);
-                S.n_oi[lane] = 0;
+                if constexpr (!kPipeC) S.n_oi[lane] = 0;
             }
             if (lane < kGroups) S.first_bad[lane] = 0xffffffffu;
             if (lane + 64 < kGroups) S.first_bad[lane + 64] = 0xffffffffu;
@@ -2420,14 +2444,42 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 S.vtot = vtot;
                 S.R = R; S.C = C; S.nstorm = nstorm; S.storm_base = storm_base; S.loc_kind = loc_kind;
                 S.lat_id = lat_id; S.prop_idx = prop_idx; S.nbig = 0; S.progressed = fastdone | (ll_prog ? 1u : 0u);
-                S.hbase = hbase; S.nh = nh; S.gap_lo = gap_lo; S.gap_hi = hbase; S.nchmax = 0;
+                S.hbase = hbase; S.nh = nh; S.gap_lo = gap_lo; S.gap_hi = hbase;
+                if constexpr (!kPipeC) S.nchmax = 0;
                 S.exit_now = done_w0;
                 if (PMODE(MODE_PROF)) S.dbg[0] += R;
             }
             ll_prog = false;
         }
+        // pipelined: barrier Y.  Every wave's stores of the previous iteration (wave 0's: its pickups', a lone message's)
+        // drain before it; behind it wave 0 publishes that iteration's counters.  MODE_PROF: the selection ends here for
+        // the phase clock, and wave 0's wait for the copying waves goes to dbg[4] alone
+        [[maybe_unused]] uint64_t y_t0 = 0;
+        if constexpr (kPipeC) {
+            if (ovl) {
+                PST(7, 3);
+                if ((PMODE(MODE_PROF)) && tid == 0) y_t0 = __builtin_amdgcn_s_memtime();
+                VM_DRAIN();
+            }
+        }
         BAR();  // selection visible
-        PST(7, 3);
+        if constexpr (kPipeC) {
+            if (w == 0) {
+                if (ovl) {
+                    if ((PMODE(MODE_PROF)) && tid == 0) {
+                        const uint64_t c_ = __builtin_amdgcn_s_memtime();
+                        S.dbg[4] += c_ - y_t0;
+                        S.prof_t = c_;
+                    }
+                    PUBLISH_PREV();
+                }
+                // this iteration's copy starts from these: their first readers stand behind phase E's barriers
+                if (lane < nout) S.out_tail0[lane] = out_tail_r;
+                if (lane == 0) S.nchmax = 0;
+            }
+        }
+        if (!ovl) PST(7, 3);
+#undef PUBLISH_PREV
         if (S.exit_now) {  // the final counters are published
             if constexpr (BULK) {
                 if (w == 0) flush_posts(S.b, P, lane);  // (phase C's last posts, e.g. a VERIFY)
@@ -3063,6 +3115,10 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 }
             }
             PST(4, 7);
+            [[maybe_unused]] uint64_t cpy_t0 = 0;
+            if constexpr (kPipeC) {
+                if ((PMODE(MODE_PROF)) && tid == 64) cpy_t0 = __builtin_amdgcn_s_memtime();
+            }
             if constexpr (BULK) {
                 if (w == 0) flush_posts(S.b, P, lane);  // this iteration's job posts, before its copies
             }
@@ -3215,7 +3271,11 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
             const uint32_t nit_r = lane < nout ? S.n_oi[lane] * nq : 0u;
             uint32_t items = 0;
             const uint32_t ibase_r = wave_excl_scan(nit_r, &items);
-            const uint32_t lo = items * (uint32_t)w / (uint32_t)kWaves, hi = items * (uint32_t)(w + 1) / (uint32_t)kWaves;
+            // (pipelined: over waves 1-7; wave 0 takes none and goes on to its pickups, consume, the poll and the selection)
+            const uint32_t lo = (kPipeC && ovl) ? (w ? items * (uint32_t)(w - 1) / (uint32_t)(kWaves - 1) : 0u)
+                                                : items * (uint32_t)w / (uint32_t)kWaves;
+            const uint32_t hi = (kPipeC && ovl) ? (w ? items * (uint32_t)w / (uint32_t)(kWaves - 1) : 0u)
+                                                : items * (uint32_t)(w + 1) / (uint32_t)kWaves;
             for (uint64_t mo = __ballot(nit_r != 0 && ibase_r < hi && ibase_r + nit_r > lo); mo; mo &= mo - 1) {
                 const int oi = __builtin_ctzll(mo);
                 const uint32_t ib = rdl32(ibase_r, oi), ie = ib + rdl32(nit_r, oi);
@@ -3388,6 +3448,13 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 }
             }
             PST(5, 7);
+            if constexpr (kPipeC) {  // MODE_PROF: the copy phase as a copying wave sees it
+                if ((PMODE(MODE_PROF)) && tid == 64) S.dbg[3] += __builtin_amdgcn_s_memtime() - cpy_t0;
+            }
+        } else if constexpr (kPipeC) {
+            // pipelined: no barrier of phases D-F stands between the other waves' reads of the selection (above) and
+            // wave 0's next one, which follows at once
+            if (ovl) BAR();
         }
 
         // every store of this iteration (payloads, votes, pickup records) drained, so the producer
@@ -3410,6 +3477,15 @@ __global__ __launch_bounds__(64 * W) void rlo_progress_kernel(Params P) {
                 if (PMODE(MODE_PROF)) atomicAdd((unsigned long long*)&S.dbg[1], (unsigned long long)adm);
             }
             PSX(4);
+            // pipelined: the in-ring heads here, not behind Y with the tails.  They are credits to the producers, for
+            // slots phase D0 staged into LDS (loaded and waited for there): nothing reads those slots again, and the
+            // wall ranks refuse ~80 messages an iteration on the rings between them for want of credits.  (A/B build,
+            // make AB=... ABFLAGS=-DRLO_AB_LATE_HEADS: behind Y; flagship 8.18 vs 7.89 ms)
+#ifndef RLO_AB_LATE_HEADS
+            if constexpr (kPipeC) {
+                if (ovl && lane < n_in2 && in_head_r != PUB_IN) { PUB_IN = in_head_r; pub64(IHPTR, in_head_r, sys); }
+            }
+#endif
             if (eager) {
                 if (lane < n_in2 && in_head_r != PUB_IN) { PUB_IN = in_head_r; pub64(IHPTR, in_head_r, sys); }
                 if (lane < n_in) {

@@ -2147,6 +2147,7 @@ static uint32_t diag_modes(uint32_t mode) {
         {"RLO_NO_HPOLLER", rlo::MODE_NOHPW},      // A/B: no wave-1 host poller
         {"RLO_HOST_DIAG", rlo::MODE_HDIAG},       // diagnostic: command-wait counters
         {"RLO_NO_NEED_TABLE", rlo::MODE_NOTAB},   // A/B, test: the storm kernel computes out-rings per message
+        {"RLO_NO_PIPELINE", rlo::MODE_NOPIPE},    // A/B, test: the 8-wave storm kernel's iteration in its serial order
     };
     static const uint32_t on = [] {  // read once per process
         uint32_t m = 0;

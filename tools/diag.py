@@ -11,7 +11,8 @@ import rlo
 PH = ["poll", "stage", "classify", "admit", "effects", "copy", "consume", "select"]
 
 
-def report(name, w, ms, deliveries):
+def report(name, w, ms, deliveries, storm8=False):
+    """storm8: an 8-wave storm -- no large-message rounds; dbg[3] / dbg[4] are the pipelined iteration's figures"""
     st = w.stats()
     it = st["iterations"].astype(np.float64)
     busy = st["busy_iterations"].astype(np.float64)
@@ -38,6 +39,13 @@ def report(name, w, ms, deliveries):
             "%d:%.1f/%.1f/%.0f" % (o, h[o] / it_r, h[32 + o] / it_r, 16 * h[64 + o] / it_r) for o in range(32) if h[32 + o] or h[o]))
         pr = st["prof"][r].astype(np.float64) / max(1, st["iterations"][r])
         print("            cycles/iter: " + "  ".join("%s %.0f" % (p, c) for p, c in zip(PH, pr)))
+        if storm8:
+            # thread 0 stamps the phases: with the pipelined iteration its "copy" is wave 0's pickups only, and the copy
+            # phase is reported by a copying wave (wave 1: copy + its pickups); wave 0's wait at barrier Y is in no phase
+            # (0 with RLO_NO_PIPELINE: the serial order has no such barrier).  The longer side bounds the iteration:
+            # wave 0 waiting = the copy, no wait = consume + poll + select
+            print("            cycles/iter: copy on wave 1 %.0f | wave 0 waits at barrier Y %.0f | wave 0 consume + poll + "
+                  "select %.0f" % (d[3] / it_r, d[4] / it_r, pr[6] + pr[0] + pr[7]))
     sys.stdout.flush()
 
 
@@ -55,7 +63,7 @@ for ln in [int(x) for x in args.lens.split(",")]:
     ms0 = w.run()
     w.program_storm(k, ln, window=win, prof=True)
     ms = w.run()
-    report("storm len=%d win=%d (%.0f/s)" % (ln, win, k / ms0 * 1e3), w, ms, k * (args.n - 1))
+    report("storm len=%d win=%d (%.0f/s)" % (ln, win, k / ms0 * 1e3), w, ms, k * (args.n - 1), storm8=w.info["waves"] == 8)
     w.close()
 if args.storm_only:
     sys.exit(0)
