@@ -322,9 +322,10 @@ def test_iar_concurrent_exact_sets(rlo, n, p, ppm, pool):
                                         (8, 1, 64), (16, 48, 64), (64, 17, 64)])
 def test_latency_program(rlo, n, ln, maxp):
     """The latency program (one bcast at a time: the doorbell path, fwd_small / ll_pass, carries every
-    message where the world has bells) at the world sizes the bench quotes p50 for, 64 B and the bell's
-    limit (112 B): per-rank delivery counts and checksums, and from a logged run every delivery's tree
-    parent and payload bytes, against the oracle (_bc_forward rootless_ops.c:1104-1225)"""
+    message of at most 8 chunks -- kBellChunks, 112 B -- where the world has bells; longer ones go through
+    the ring alone, tests/test_gpu_bcast_lengths.py) at the world sizes the bench quotes p50 for, 64 B and
+    the bell's limit (112 B): per-rank delivery counts and checksums, and from a logged run every delivery's
+    tree parent and payload bytes, against the oracle (_bc_forward rootless_ops.c:1104-1225)"""
     rounds, seed = 64, 5
     with rlo.World(n, max_payload=maxp) as w:
         if maxp <= 112:
