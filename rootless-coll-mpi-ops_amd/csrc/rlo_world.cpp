@@ -916,6 +916,74 @@ OwnLists<Off> own_lists(const rlo_world* w, int64_t k, Origin origin_of, Place p
     return o;
 }
 
+// The three send programs (rlo_hip.h rlo_send_cfg_t, rlo_send_bulk_cfg_t, rlo_send_storm_cfg_t; what tells them apart:
+// DESIGN.md 4.0.2a) as one description: send_desc() converts a public cfg, send_check() refuses what can be refused
+// without a GPU, send_setup() loads the program.  What their callers rely on:
+//  - send_check refuses k out of range and origin == NULL BEFORE it reads an element of origin / len;
+//  - every refusal (the entry point's world refusals, send_check, RLO_E_NOTCONNECTED) returns before send_setup's
+//    base_params(w), so a refused program leaves the previous one runnable; every RLO_E_INVAL condition precedes
+//    RLO_E_NOTCONNECTED;
+//  - send_setup fills the lengths beside the own lists through own_lists' place callback, uploads into the buffers of
+//    its kind (hop, bulk: d_lat_own_off / d_lat_own / d_send_own_len; storm: d_sched_off / d_sched_ids / d_sched_len),
+//    and sets the Params fields and w->lat_rounds of its kind and no others
+enum SendKind { kSendHop, kSendBulk, kSendStorm };
+struct SendDesc {  // (send_desc fills it in this order)
+    int64_t k, k_max;  // messages, 1 .. k_max
+    const int32_t* origin;
+    const uint32_t* len;
+    const void* src;
+    void* dst;
+    uint64_t place, place_max;  // bytes per message place (slot / stride): a multiple of 16, < 2^32, <= place_max ...
+    bool place_max_no_len;      // ... the latter only where len == NULL (bulk: with lengths the stride is a distance)
+    uint64_t len_max;           // len[i] in 1 .. len_max
+    bool has_rank_stride;       // (hop has none: local rank lr's place of message i is (lr * k + i) * place)
+    uint64_t rank_stride;       // 0 = k * place
+    uint32_t allowed, flags, log_cap, window;
+};
+
+constexpr uint64_t round16(uint64_t x) { return (x + 15u) & ~15ull; }
+
+SendDesc send_desc(const rlo_send_cfg_t& c, uint32_t max_payload) {  // (1008: 63 chunks + the header, the hop kernel's lanes)
+    return {c.k, 0x7FFFFFFFll, c.origin, c.len, c.src, c.dst, c.slot, std::min<uint64_t>(1008u, round16(max_payload)), false,
+            c.slot, false, 0, RLO_FLAG_LOG | RLO_FLAG_HIST | RLO_SEND_ORDERED, c.flags, c.log_cap, 0};
+}
+SendDesc send_desc(const rlo_send_bulk_cfg_t& c, uint64_t bulk_max) {  // (bulk_max 0, no bulk messages: no length fits)
+    return {c.k, 0x7FFFFFFFll, c.origin, c.len, c.src, c.dst, c.stride, bulk_max, true,
+            std::min(c.stride, bulk_max), true, c.rank_stride, RLO_FLAG_LOG | RLO_FLAG_HIST, c.flags, c.log_cap, 0};
+}
+SendDesc send_desc(const rlo_send_storm_cfg_t& c, uint32_t max_payload) {
+    const uint64_t cap = round16(max_payload);  // what a ring slot of the world carries; beyond 65520: no storm send
+    return {c.k, 0xFFFFFFFFll, c.origin, c.len, c.src, c.dst, c.slot, cap <= 65520u ? cap : 0, false,
+            c.slot, true, c.rank_stride, RLO_FLAG_LOG | RLO_FLAG_HIST | RLO_FLAG_PROF, c.flags, c.log_cap, c.window};
+}
+
+int send_check(const SendDesc* cfg, int n_ranks) {
+    if (n_ranks < 1 || cfg->k < 1 || cfg->k > cfg->k_max || !cfg->origin) return RLO_E_INVAL;
+    if (cfg->place == 0 || (cfg->place & 15u) || cfg->place >= (1ull << 32)) return RLO_E_INVAL;
+    if (cfg->place > cfg->place_max && !(cfg->place_max_no_len && cfg->len)) return RLO_E_INVAL;
+    if (!cfg->src || !cfg->dst || ((uintptr_t)cfg->src & 15u) || ((uintptr_t)cfg->dst & 15u)) return RLO_E_INVAL;
+    if (cfg->flags & ~cfg->allowed) return RLO_E_INVAL;
+    for (int64_t i = 0; i < cfg->k; i++) {
+        if (cfg->origin[i] < 0 || cfg->origin[i] >= n_ranks) return RLO_E_INVAL;
+        if (cfg->len && (cfg->len[i] == 0 || cfg->len[i] > cfg->len_max)) return RLO_E_INVAL;
+    }
+    if (cfg->rank_stride) {  // a rank's places must hold its last message
+        const uint64_t last = cfg->len ? round16(cfg->len[cfg->k - 1]) : cfg->place;
+        if ((cfg->rank_stride & 15u) || cfg->rank_stride < (uint64_t)(cfg->k - 1) * cfg->place + last) return RLO_E_INVAL;
+    }
+    return RLO_OK;
+}
+
+// the own lists of a send program and the lengths beside them, into the buffers the program's kernel reads
+template <class Off>
+int send_lists(rlo_world* w, const SendDesc& d, DevBuf<Off>& off, DevBuf<uint32_t>& idx, DevBuf<uint32_t>& len) {
+    std::vector<uint32_t> own_len((size_t)d.k, 0);
+    const auto own = own_lists<Off>(w, d.k, [&](int64_t i) { return d.origin[i]; },
+                                    [&](size_t at, int64_t i) { own_len[at] = d.len ? d.len[i] : (uint32_t)d.place; });
+    own_len.resize(own.idx.size());
+    return off.upload(own.off) || idx.upload(own.idx) || len.upload(own_len) || w->d_expect_bcast.upload(own.expect);
+}
+
 }  // namespace
 
 // ====================================================================== C ABI
@@ -1533,176 +1601,103 @@ int rlo_program_latency(rlo_world_t* w, uint32_t rounds, uint32_t len, uint64_t 
     return RLO_OK;
 }
 
-// the send program (rlo_hip.h rlo_send_cfg_t): what can be refused without a GPU
+// the send programs: what can be refused without a GPU (send_check)
 int rlo_send_check(const rlo_send_cfg_t* cfg, int n_ranks, uint32_t max_payload) {
-    if (!cfg || n_ranks < 1 || cfg->k < 1 || cfg->k > 0x7FFFFFFFll || !cfg->origin) return RLO_E_INVAL;
-    const uint32_t slot = cfg->slot;
-    if (slot == 0 || (slot & 15u) || slot > 1008u || slot > (((uint64_t)max_payload + 15u) & ~15ull)) return RLO_E_INVAL;
-    if (!cfg->src || !cfg->dst || ((uintptr_t)cfg->src & 15u) || ((uintptr_t)cfg->dst & 15u)) return RLO_E_INVAL;
-    if (cfg->flags & ~(RLO_FLAG_LOG | RLO_FLAG_HIST | RLO_SEND_ORDERED)) return RLO_E_INVAL;
-    for (int64_t i = 0; i < cfg->k; i++) {
-        if (cfg->origin[i] < 0 || cfg->origin[i] >= n_ranks) return RLO_E_INVAL;
-        if (cfg->len && (cfg->len[i] == 0 || cfg->len[i] > slot)) return RLO_E_INVAL;
-    }
-    return RLO_OK;
+    const SendDesc d = cfg ? send_desc(*cfg, max_payload) : SendDesc{};  // (no cfg: no messages)
+    return send_check(&d, n_ranks);
 }
 
-int rlo_program_send(rlo_world_t* w, const rlo_send_cfg_t* cfg) {
-    if (!w || !cfg) return RLO_E_INVAL;
-    int rc = rlo_send_check(cfg, w->L.n, w->max_payload);
-    if (rc) return rc;
-    if (w->d_xcd) return RLO_E_INVAL;  // RLO_PART_ONE_XCD: refused (rlo_hip.h)
-    const bool ordered = (cfg->flags & RLO_SEND_ORDERED) != 0;
-    // ordered, sharded: the round word and counts are part 0's copy (rlo_device.hpp kLatWords)
-    if (ordered && w->L.nparts != 1 && cfg->k > rlo::kLatCap) return RLO_E_INVAL;
-    if (!w->connected) return RLO_E_NOTCONNECTED;
+int rlo_send_bulk_check(const rlo_send_bulk_cfg_t* cfg, int n_ranks, uint64_t bulk_max) {
+    const SendDesc d = cfg ? send_desc(*cfg, bulk_max) : SendDesc{};
+    return send_check(&d, n_ranks);
+}
+
+int rlo_send_storm_check(const rlo_send_storm_cfg_t* cfg, int n_ranks, uint32_t max_payload) {
+    const SendDesc d = cfg ? send_desc(*cfg, max_payload) : SendDesc{};  // (no cfg: no messages)
+    return send_check(&d, n_ranks);
+}
+
+// load the send program d, checked (send_check) in a connected world that runs its kind
+static int send_setup(rlo_world* w, const SendDesc& d, SendKind kind) {
     base_params(w);
     rlo::Params& P = w->P;
-    const uint32_t k = (uint32_t)cfg->k;
-    // per local rank the messages it originates, in order, and their lengths (the kernel loads 64 at a time)
-    const auto own = own_lists<uint32_t>(w, k, [&](int64_t i) { return cfg->origin[i]; });
-    std::vector<uint32_t> own_len(own.idx.size(), 0);
-    for (size_t at = 0; at < (size_t)own.off[w->nl]; at++) own_len[at] = cfg->len ? cfg->len[own.idx[at]] : cfg->slot;
-    if (w->d_lat_own_off.upload(own.off) || w->d_lat_own.upload(own.idx) || w->d_send_own_len.upload(own_len) ||
-        w->d_expect_bcast.upload(own.expect))
-        return RLO_E_HIP;
-    // (MODE_LL: the hop kernel always rings the doorbells, and only that kernel runs this program; rlo_send_check
-    // refused RLO_FLAG_PROF)
-    P.mode = rlo::MODE_SEND | rlo::MODE_LL | (ordered ? rlo::MODE_LAT : 0u) | flag_modes(cfg->flags);
-    P.len = cfg->slot;
-    P.hop_chunks = 1u + cfg->slot / 16u;
-    P.lat_own_off = w->d_lat_own_off.p;
-    P.lat_own = w->d_lat_own.p;
-    P.send_own_len = w->d_send_own_len.p;
+    const uint32_t place = (uint32_t)d.place;
+    // per local rank the messages it originates, in order, and their lengths beside them
+    if (kind == kSendStorm) {  // the storm's own lists
+        if (send_lists(w, d, w->d_sched_off, w->d_sched_ids, w->d_sched_len)) return RLO_E_HIP;
+        P.sched_off = w->d_sched_off.p, P.sched_ids = w->d_sched_ids.p, P.sched_len = w->d_sched_len.p;
+    } else {  // the closed loop's (the hop kernel loads 64 at a time)
+        if (send_lists(w, d, w->d_lat_own_off, w->d_lat_own, w->d_send_own_len)) return RLO_E_HIP;
+        P.lat_own_off = w->d_lat_own_off.p, P.lat_own = w->d_lat_own.p, P.send_own_len = w->d_send_own_len.p;
+    }
     P.expect_bcast = w->d_expect_bcast.p;
-    P.send_src = static_cast<const uint8_t*>(cfg->src);
-    P.send_dst = static_cast<uint8_t*>(cfg->dst);
-    P.send_k = k;
-    P.send_slot = cfg->slot;
+    P.send_src = static_cast<const uint8_t*>(d.src);
+    P.send_dst = static_cast<uint8_t*>(d.dst);
+    P.send_k = (uint32_t)d.k;
+    if (d.has_rank_stride) P.send_rank_stride = d.rank_stride ? d.rank_stride : (uint64_t)d.k * d.place;
+    bool closed = false;  // message i+1 originates when every rank has picked up message i (closed_loop)
+    switch (kind) {
+    case kSendHop:
+        // (MODE_LL: the hop kernel always rings the doorbells, and only that kernel runs this program; send_check
+        // refused RLO_FLAG_PROF)
+        closed = (d.flags & RLO_SEND_ORDERED) != 0;
+        P.mode = rlo::MODE_SEND | rlo::MODE_LL | (closed ? rlo::MODE_LAT : 0u);
+        P.len = P.send_slot = place;
+        P.hop_chunks = 1u + place / 16u;
+        break;
+    case kSendBulk:
+        // (the launch adds MODE_LAT for the kernel -- the program is the latency program's loop -- but the pick sees
+        // MODE_SENDB alone: rlo_pick_progress)
+        closed = true;
+        P.mode = rlo::MODE_SENDB | rlo::MODE_LL;
+        P.send_stride = d.place;
+        break;
+    case kSendStorm:
+        // (the launch adds MODE_STORM for the kernel -- the program is the storm's open loop -- but the pick sees
+        // MODE_SENDS alone: rlo_pick_progress.  No doorbells: the storm never runs with them)
+        P.mode = rlo::MODE_SENDS;
+        P.len = P.len_lo = P.len_hi = P.send_slot = place;
+        P.window = std::min<uint32_t>(d.window ? d.window : 64, 64u);  // one wave prefetches the ids and lengths
+        break;
+    }
+    P.mode |= flag_modes(d.flags);
     w->lat_rounds = 0;
     w->tl_rows = 0;
-    if (ordered && closed_loop(w, k)) return RLO_E_HIP;
-    rc = setup_log(w, cfg->flags, cfg->log_cap, false);  // records only: dst is the payload
+    if (closed && closed_loop(w, (uint32_t)d.k)) return RLO_E_HIP;
+    const int rc = setup_log(w, d.flags, d.log_cap, false);  // records only: dst is the payload
     if (rc) return rc;
     w->have_program = true;
     return RLO_OK;
 }
 
-// the bulk send program (rlo_hip.h rlo_send_bulk_cfg_t): what can be refused without a GPU
-int rlo_send_bulk_check(const rlo_send_bulk_cfg_t* cfg, int n_ranks, uint64_t bulk_max) {
-    if (!cfg || n_ranks < 1 || bulk_max == 0 || cfg->k < 1 || cfg->k > 0x7FFFFFFFll || !cfg->origin) return RLO_E_INVAL;
-    const uint64_t stride = cfg->stride;
-    if (stride == 0 || (stride & 15u) || stride >= (1ull << 32)) return RLO_E_INVAL;
-    if (!cfg->len && stride > bulk_max) return RLO_E_INVAL;  // (every message is `stride` bytes)
-    if (!cfg->src || !cfg->dst || ((uintptr_t)cfg->src & 15u) || ((uintptr_t)cfg->dst & 15u)) return RLO_E_INVAL;
-    if (cfg->flags & ~(RLO_FLAG_LOG | RLO_FLAG_HIST)) return RLO_E_INVAL;
-    for (int64_t i = 0; i < cfg->k; i++) {
-        if (cfg->origin[i] < 0 || cfg->origin[i] >= n_ranks) return RLO_E_INVAL;
-        if (cfg->len && (cfg->len[i] == 0 || cfg->len[i] > stride || cfg->len[i] > bulk_max)) return RLO_E_INVAL;
-    }
-    if (cfg->rank_stride) {  // a rank's places must hold its last message
-        const uint64_t last = cfg->len ? ((uint64_t)cfg->len[cfg->k - 1] + 15u) & ~15ull : stride;
-        if ((cfg->rank_stride & 15u) || cfg->rank_stride < (uint64_t)(cfg->k - 1) * stride + last) return RLO_E_INVAL;
-    }
-    return RLO_OK;
+// the world's refusals, the arguments', RLO_E_NOTCONNECTED, and only then the previous program goes
+static int send_program(rlo_world* w, const SendDesc& d, SendKind kind) {
+    const int rc = send_check(&d, w->L.n);
+    if (rc) return rc;
+    return w->connected ? send_setup(w, d, kind) : RLO_E_NOTCONNECTED;
+}
+
+int rlo_program_send(rlo_world_t* w, const rlo_send_cfg_t* cfg) {
+    if (!w || !cfg || w->d_xcd) return RLO_E_INVAL;  // RLO_PART_ONE_XCD: refused (rlo_hip.h)
+    // ordered, sharded: the round word and counts are part 0's copy (rlo_device.hpp kLatWords)
+    if ((cfg->flags & RLO_SEND_ORDERED) && w->L.nparts != 1 && cfg->k > rlo::kLatCap) return RLO_E_INVAL;
+    return send_program(w, send_desc(*cfg, w->max_payload), kSendHop);
 }
 
 int rlo_program_send_bulk(rlo_world_t* w, const rlo_send_bulk_cfg_t* cfg) {
     if (!w || !cfg || !w->L.bulk_max) return RLO_E_INVAL;  // (a world without bulk messages: rlo_program_send's)
-    int rc = rlo_send_bulk_check(cfg, w->L.n, w->L.bulk_max);
-    if (rc) return rc;
     // the round word and counts of a world of several parts are part 0's copy (rlo_device.hpp kLatWords)
     if (w->L.nparts != 1 && cfg->k > rlo::kLatCap) return RLO_E_INVAL;
     // one instantiation runs it, the bulk kernel with doorbells: a world whose ranks that kernel cannot hold
     // co-resident (rlo_world_info_t.ll_ok == 0) has no bulk send
     if (!ll_mode(w, 0) || w->d_xcd) return RLO_E_INVAL;
-    if (!w->connected) return RLO_E_NOTCONNECTED;
-    base_params(w);
-    rlo::Params& P = w->P;
-    const uint32_t k = (uint32_t)cfg->k;
-    const auto own = own_lists<uint32_t>(w, k, [&](int64_t i) { return cfg->origin[i]; });
-    std::vector<uint32_t> own_len(own.idx.size(), 0);
-    for (size_t at = 0; at < (size_t)own.off[w->nl]; at++)
-        own_len[at] = cfg->len ? cfg->len[own.idx[at]] : (uint32_t)cfg->stride;
-    if (w->d_lat_own_off.upload(own.off) || w->d_lat_own.upload(own.idx) || w->d_send_own_len.upload(own_len) ||
-        w->d_expect_bcast.upload(own.expect) || closed_loop(w, k))
-        return RLO_E_HIP;
-    // (the launch adds MODE_LAT for the kernel -- the program is the latency program's loop -- but the pick sees
-    // MODE_SENDB alone: rlo_pick_progress)
-    P.mode = rlo::MODE_SENDB | rlo::MODE_LL | flag_modes(cfg->flags);
-    P.lat_own_off = w->d_lat_own_off.p;
-    P.lat_own = w->d_lat_own.p;
-    P.send_own_len = w->d_send_own_len.p;
-    P.expect_bcast = w->d_expect_bcast.p;
-    P.send_src = static_cast<const uint8_t*>(cfg->src);
-    P.send_dst = static_cast<uint8_t*>(cfg->dst);
-    P.send_k = k;
-    P.send_stride = cfg->stride;
-    P.send_rank_stride = cfg->rank_stride ? cfg->rank_stride : (uint64_t)k * cfg->stride;
-    w->tl_rows = 0;
-    rc = setup_log(w, cfg->flags, cfg->log_cap, false);  // records only: dst is the payload
-    if (rc) return rc;
-    w->have_program = true;
-    return RLO_OK;
-}
-
-// the storm send program (rlo_hip.h rlo_send_storm_cfg_t): what can be refused without a GPU
-int rlo_send_storm_check(const rlo_send_storm_cfg_t* cfg, int n_ranks, uint32_t max_payload) {
-    if (!cfg || n_ranks < 1 || cfg->k < 1 || cfg->k > 0xFFFFFFFFll || !cfg->origin) return RLO_E_INVAL;
-    const uint32_t slot = cfg->slot;
-    const uint64_t cap = ((uint64_t)max_payload + 15u) & ~15ull;  // (what a ring slot of the world carries)
-    if (slot == 0 || (slot & 15u) || slot > cap || cap > 65520u) return RLO_E_INVAL;
-    if (!cfg->src || !cfg->dst || ((uintptr_t)cfg->src & 15u) || ((uintptr_t)cfg->dst & 15u)) return RLO_E_INVAL;
-    if (cfg->flags & ~(RLO_FLAG_LOG | RLO_FLAG_HIST | RLO_FLAG_PROF)) return RLO_E_INVAL;
-    for (int64_t i = 0; i < cfg->k; i++) {
-        if (cfg->origin[i] < 0 || cfg->origin[i] >= n_ranks) return RLO_E_INVAL;
-        if (cfg->len && (cfg->len[i] == 0 || cfg->len[i] > slot)) return RLO_E_INVAL;
-    }
-    if (cfg->rank_stride) {  // a rank's places must hold its last message
-        const uint64_t last = cfg->len ? ((uint64_t)cfg->len[cfg->k - 1] + 15u) & ~15ull : slot;
-        if ((cfg->rank_stride & 15u) || cfg->rank_stride < (uint64_t)(cfg->k - 1) * slot + last) return RLO_E_INVAL;
-    }
-    return RLO_OK;
+    return send_program(w, send_desc(*cfg, w->L.bulk_max), kSendBulk);
 }
 
 int rlo_program_send_storm(rlo_world_t* w, const rlo_send_storm_cfg_t* cfg) {
-    if (!w || !cfg) return RLO_E_INVAL;
     // (a world with bulk messages has rlo_program_send_bulk; RLO_PART_ONE_XCD worlds run the hop kernel or nothing)
-    if (w->L.bulk_max || w->d_xcd) return RLO_E_INVAL;
-    int rc = rlo_send_storm_check(cfg, w->L.n, w->max_payload);
-    if (rc) return rc;
-    if (!w->connected) return RLO_E_NOTCONNECTED;
-    base_params(w);
-    rlo::Params& P = w->P;
-    // per local rank the messages it originates, ascending, and their lengths beside them (the storm's own lists)
-    std::vector<uint32_t> own_len;
-    const auto own = own_lists<int64_t>(w, cfg->k, [&](int64_t i) { return cfg->origin[i]; });
-    own_len.assign(own.idx.size(), 0);
-    for (size_t at = 0; at < (size_t)own.off[w->nl]; at++) own_len[at] = cfg->len ? cfg->len[own.idx[at]] : cfg->slot;
-    if (w->d_sched_off.upload(own.off) || w->d_sched_ids.upload(own.idx) || w->d_sched_len.upload(own_len) ||
-        w->d_expect_bcast.upload(own.expect))
-        return RLO_E_HIP;
-    // (the launch adds MODE_STORM for the kernel -- the program is the storm's open loop -- but the pick sees
-    // MODE_SENDS alone: rlo_pick_progress.  No doorbells: the storm never runs with them)
-    P.mode = rlo::MODE_SENDS | flag_modes(cfg->flags);
-    P.len = cfg->slot;
-    P.len_lo = P.len_hi = cfg->slot;
-    P.window = std::min<uint32_t>(cfg->window ? cfg->window : 64, 64u);  // one wave prefetches the ids and lengths
-    P.sched_off = w->d_sched_off.p;
-    P.sched_ids = w->d_sched_ids.p;
-    P.sched_len = w->d_sched_len.p;
-    P.expect_bcast = w->d_expect_bcast.p;
-    P.send_src = static_cast<const uint8_t*>(cfg->src);
-    P.send_dst = static_cast<uint8_t*>(cfg->dst);
-    P.send_k = (uint32_t)cfg->k;
-    P.send_slot = cfg->slot;
-    P.send_rank_stride = cfg->rank_stride ? cfg->rank_stride : (uint64_t)cfg->k * cfg->slot;
-    w->lat_rounds = 0;
-    w->tl_rows = 0;
-    rc = setup_log(w, cfg->flags, cfg->log_cap, false);  // records only: dst is the payload
-    if (rc) return rc;
-    w->have_program = true;
-    return RLO_OK;
+    if (!w || !cfg || w->L.bulk_max || w->d_xcd) return RLO_E_INVAL;
+    return send_program(w, send_desc(*cfg, w->max_payload), kSendStorm);
 }
 
 // the device judge registry (rlo_kernel.hip judge_eval) and its per-rank tables, for every world

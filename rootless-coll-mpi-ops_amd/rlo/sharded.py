@@ -82,6 +82,11 @@ class _HipBuf:
             self.p = ctypes.c_void_p()
 
 
+# the send programs' specs: kind -> (the World's method, the spec's key of the message place, further keys: defaults)
+_SEND = {"send": ("program_send", "slot", {"ordered": False}), "send_bulk": ("program_send_bulk", "stride", {}),
+         "send_storm": ("program_send_storm", "slot", {"window": 64})}
+
+
 def _program(w, spec):
     if spec["kind"] == "storm":
         w.program_storm(spec["k"], spec["len"], seed=spec.get("seed", 0x5EED), window=spec.get("window", 64),
@@ -94,39 +99,18 @@ def _program(w, spec):
                       log=spec.get("log", False), log_cap=spec.get("log_cap", 0), pool=spec.get("pool", 1))
     elif spec["kind"] == "lat":
         w.program_latency(spec["rounds"], spec["len"], seed=spec.get("seed", 0x5EED))
-    elif spec["kind"] == "send":
+    elif spec["kind"] in _SEND:
         # the part's own device buffers: the whole source (a part reads only its own ranks' messages) and its ranks'
-        # destination places, pre-filled; both are in place before the launch (which runs on a stream of its own)
-        import torch
-
-        dev = torch.device("cuda", w.device if w.device >= 0 else torch.cuda.current_device())
-        k, slot = len(spec["origins"]), spec["slot"]
-        src = torch.from_numpy(np.ascontiguousarray(spec["src"], dtype=np.uint8).reshape(-1)).to(dev)
-        dst = torch.full((w.n_local * k * slot,), spec.get("fill", 0xA5), dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        w._send_bufs = (src, dst)
-        w.program_send(spec["origins"], src, dst, slot, lens=spec.get("lens"), ordered=spec.get("ordered", False),
-                       log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False))
-    elif spec["kind"] == "send_storm":  # buffers as for "send" (parts of one process)
-        import torch
-
-        dev = torch.device("cuda", w.device if w.device >= 0 else torch.cuda.current_device())
-        k, slot = len(spec["origins"]), spec["slot"]
-        src = torch.from_numpy(np.ascontiguousarray(spec["src"], dtype=np.uint8).reshape(-1)).to(dev)
-        dst = torch.full((w.n_local * k * slot,), spec.get("fill", 0xA5), dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        w._send_bufs = (src, dst)
-        w.program_send_storm(spec["origins"], src, dst, slot, lens=spec.get("lens"), window=spec.get("window", 64),
-                             log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False))
-    elif spec["kind"] == "send_bulk":
-        # the part's own device buffers, as for "send", but allocated through the HIP runtime the engine itself uses: a
-        # spawned part process has no other (torch found no GPU there once the engine's runtime was up)
-        k, stride = len(spec["origins"]), spec["stride"]
+        # destination places, pre-filled; both are in place before the launch (which runs on a stream of its own).
+        # Allocated through the HIP runtime the engine itself uses: a spawned part process has no other (torch found
+        # no GPU there once the engine's runtime was up)
+        method, place, extra = _SEND[spec["kind"]]
         src = _HipBuf(w.device, np.ascontiguousarray(spec["src"], dtype=np.uint8).reshape(-1))
-        dst = _HipBuf(w.device, w.n_local * k * stride, fill=spec.get("fill", 0xA5))
+        dst = _HipBuf(w.device, w.n_local * len(spec["origins"]) * spec[place], fill=spec.get("fill", 0xA5))
         w._send_bufs = (src, dst)
-        w.program_send_bulk(spec["origins"], src.extent(), dst.extent(), stride, lens=spec.get("lens"),
-                            log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False))
+        getattr(w, method)(spec["origins"], src.extent(), dst.extent(), spec[place], lens=spec.get("lens"),
+                           log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False),
+                           **{key: spec.get(key, default) for key, default in extra.items()})
     else:
         raise ValueError(spec["kind"])
 
@@ -137,10 +121,8 @@ def _collect(w, spec):
     out = {"rank_begin": w.rank_begin, "stats": st, "ms": w.kernel_ms(), "info": dict(w.info)}
     if spec["kind"] == "lat" and w.rank_begin == 0:
         out["rounds"] = w.round_ticks()
-    if spec["kind"] in ("send", "send_storm"):  # this part's destination buffer: [local rank][message][slot] bytes
-        out["dst"] = w._send_bufs[1].cpu().numpy().reshape(w.n_local, len(spec["origins"]), spec["slot"])
-    if spec["kind"] == "send_bulk":
-        out["dst"] = w._send_bufs[1].download().reshape(w.n_local, len(spec["origins"]), spec["stride"])
+    if spec["kind"] in _SEND:  # this part's destination buffer: [local rank][message][place] bytes
+        out["dst"] = w._send_bufs[1].download().reshape(w.n_local, len(spec["origins"]), spec[_SEND[spec["kind"]][1]])
         for b in w._send_bufs:
             b.free()
     if spec.get("log"):

@@ -193,29 +193,10 @@ class World:
         pair; src holds k * slot bytes, dst n_local * k * slot, both 16-B aligned.  ordered: one message in flight (a
         total order; latencies_ticks() as for the latency program).  Only the hop kernel runs this program: a launch
         that cannot run it raises."""
-        origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
-        k = int(origin.size)
-        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
-        if ln is not None and ln.size != k:
-            raise ValueError("program_send: %d lengths for %d messages" % (ln.size, k))
-        sp, sn = _dev_extent(src)
-        dp, dn = _dev_extent(dst)
-        if sp % 16 or dp % 16:
-            raise ValueError("program_send: src and dst must be 16-byte aligned")
-        if sn < k * slot or dn < self.n_local * k * slot:
-            raise ValueError("program_send: src holds %d bytes (needs %d), dst %d (needs %d)" %
-                             (sn, k * slot, dn, self.n_local * k * slot))
-        cfg = L.SendCfg()
-        cfg.k = k
-        cfg.origin = origin.ctypes.data
-        cfg.len = None if ln is None else ln.ctypes.data
-        cfg.src, cfg.dst = sp, dp
-        cfg.slot = slot
-        cfg.flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0) | (L.RLO_SEND_ORDERED if ordered else 0)
-        cfg.log_cap = log_cap
-        self._keep = [origin, ln, src, dst, cfg]
+        flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0) | (L.RLO_SEND_ORDERED if ordered else 0)
+        cfg, self._keep = _send_cfg("send", origins, src, dst, slot, lens, 0, 0, flags, log_cap, self.n_local)
         check(self.lib.rlo_program_send(self.h, ctypes.byref(cfg)), "rlo_program_send")
-        self._lat_rounds = k if ordered else 0
+        self._lat_rounds = cfg.k if ordered else 0
 
     def program_send_bulk(self, origins, src, dst, stride, lens=None, rank_stride=0, log=False, hist=False, log_cap=0):
         """rlo_program_send_bulk (worlds with bulk messages): message i (len(origins) of them, closed loop) is a bulk
@@ -223,31 +204,10 @@ class World:
         lr's copy lands at dst + lr * rank_stride + i * stride (rank_stride 0: k * stride), DEVICE memory.  src / dst
         as for program_send, 16-B aligned; src is read for round16(lens[i]) bytes of each message.  latencies_ticks()
         as for a bulk round of the latency program."""
-        origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
-        k = int(origin.size)
-        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
-        if ln is not None and ln.size != k:
-            raise ValueError("program_send_bulk: %d lengths for %d messages" % (ln.size, k))
-        sp, sn = _dev_extent(src)
-        dp, dn = _dev_extent(dst)
-        if k and stride > 0 and stride % 16 == 0 and rank_stride % 16 == 0:
-            # the buffers hold what the program reads and writes (the argument ranges themselves: rlo_send_bulk_check)
-            last = -(-int(ln[-1] if ln is not None else stride) // 16) * 16
-            rs = rank_stride or k * stride
-            if sn < (k - 1) * stride + last or dn < (self.n_local - 1) * rs + (k - 1) * stride + last:
-                raise ValueError("program_send_bulk: src holds %d bytes, dst %d: too small for %d messages of stride %d"
-                                 % (sn, dn, k, stride))
-        cfg = L.SendBulkCfg()
-        cfg.k = k
-        cfg.origin = origin.ctypes.data
-        cfg.len = None if ln is None else ln.ctypes.data
-        cfg.src, cfg.dst = sp, dp
-        cfg.stride, cfg.rank_stride = stride, rank_stride
-        cfg.flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0)
-        cfg.log_cap = log_cap
-        self._keep = [origin, ln, src, dst, cfg]
+        flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0)
+        cfg, self._keep = _send_cfg("send_bulk", origins, src, dst, stride, lens, rank_stride, 0, flags, log_cap, self.n_local)
         check(self.lib.rlo_program_send_bulk(self.h, ctypes.byref(cfg)), "rlo_program_send_bulk")
-        self._lat_rounds = k
+        self._lat_rounds = cfg.k
 
     def program_send_storm(self, origins, src, dst, slot, lens=None, rank_stride=0, window=64, log=False, hist=False,
                            log_cap=0, prof=False):
@@ -256,29 +216,9 @@ class World:
         rank lr's copy lands at dst + lr * rank_stride + i * slot (rank_stride 0: k * slot), DEVICE memory.  slot: a
         multiple of 16, at most the world's max_payload.  src / dst as for program_send, 16-B aligned; src is read for
         round16(lens[i]) bytes of each message.  The progress kernel's storm-send instantiation runs it."""
-        origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
-        k = int(origin.size)
-        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
-        if ln is not None and ln.size != k:
-            raise ValueError("program_send_storm: %d lengths for %d messages" % (ln.size, k))
-        sp, sn = _dev_extent(src)
-        dp, dn = _dev_extent(dst)
-        if k and slot > 0 and slot % 16 == 0 and rank_stride % 16 == 0:
-            # the buffers hold what the program reads and writes (the argument ranges themselves: rlo_send_storm_check)
-            last = -(-int(ln[-1] if ln is not None else slot) // 16) * 16
-            rs = rank_stride or k * slot
-            if sn < (k - 1) * slot + last or dn < (self.n_local - 1) * rs + (k - 1) * slot + last:
-                raise ValueError("program_send_storm: src holds %d bytes, dst %d: too small for %d messages of slot %d"
-                                 % (sn, dn, k, slot))
-        cfg = L.SendStormCfg()
-        cfg.k = k
-        cfg.origin = origin.ctypes.data
-        cfg.len = None if ln is None else ln.ctypes.data
-        cfg.src, cfg.dst = sp, dp
-        cfg.slot, cfg.window, cfg.rank_stride = slot, window, rank_stride
-        cfg.flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0) | (L.RLO_FLAG_PROF if prof else 0)
-        cfg.log_cap = log_cap
-        self._keep = [origin, ln, src, dst, cfg]
+        flags = (L.RLO_FLAG_LOG if log else 0) | (L.RLO_FLAG_HIST if hist else 0) | (L.RLO_FLAG_PROF if prof else 0)
+        cfg, self._keep = _send_cfg("send_storm", origins, src, dst, slot, lens, rank_stride, window, flags, log_cap,
+                                    self.n_local)
         check(self.lib.rlo_program_send_storm(self.h, ctypes.byref(cfg)), "rlo_program_send_storm")
         self._lat_rounds = 0
 
@@ -483,6 +423,50 @@ def _dev_extent(x):
     return int(x.data_ptr()), int(x.numel()) * int(x.element_size())
 
 
+# the send programs' cfgs: kind -> (the mirror, its field of the message place)
+_SEND_CFG = {"send": (L.SendCfg, "slot"), "send_bulk": (L.SendBulkCfg, "stride"), "send_storm": (L.SendStormCfg, "slot")}
+
+
+def _send_cfg(kind, origins, src, dst, place, lens, rank_stride, window, flags, log_cap, n_local=None):
+    """(cfg, what it points into) of a send program.  n_local: the local ranks of the world that is to run it -- src /
+    dst are device buffers (_dev_extent) that must hold what the program reads and writes; None: the check wrappers'
+    pointers as integers.  The argument ranges themselves are the library's (rlo_send_check and its kin)"""
+    who = kind + "_check" if n_local is None else "program_" + kind
+    struct, field = _SEND_CFG[kind]
+    origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
+    k = int(origin.size)
+    ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
+    if ln is not None and ln.size != k:
+        raise ValueError("%s: %d lengths for %d messages" % (who, ln.size, k))
+    sp, dp = src, dst
+    if n_local is not None:
+        (sp, sn), (dp, dn) = _dev_extent(src), _dev_extent(dst)
+        if kind == "send":
+            if sp % 16 or dp % 16:
+                raise ValueError("program_send: src and dst must be 16-byte aligned")
+            if sn < k * place or dn < n_local * k * place:
+                raise ValueError("program_send: src holds %d bytes (needs %d), dst %d (needs %d)" %
+                                 (sn, k * place, dn, n_local * k * place))
+        elif k and place > 0 and place % 16 == 0 and rank_stride % 16 == 0:  # (else: the library's RloError)
+            last = -(-int(ln[-1] if ln is not None else place) // 16) * 16
+            rs = rank_stride or k * place
+            if sn < (k - 1) * place + last or dn < (n_local - 1) * rs + (k - 1) * place + last:
+                raise ValueError("%s: src holds %d bytes, dst %d: too small for %d messages of %s %d"
+                                 % (who, sn, dn, k, field, place))
+    cfg = struct()
+    cfg.k = k
+    cfg.origin = origin.ctypes.data if k else None
+    cfg.len = None if ln is None or not k else ln.ctypes.data
+    cfg.src, cfg.dst = sp, dp
+    setattr(cfg, field, place)
+    if kind != "send":
+        cfg.rank_stride = rank_stride
+    if kind == "send_storm":
+        cfg.window = window
+    cfg.flags, cfg.log_cap = flags, log_cap
+    return cfg, [origin, ln, src, dst, cfg]
+
+
 def send_fragments(nbytes, slot=1008):
     """the (offset, len) fragments of at most `slot` bytes that cover nbytes, in order (only the last is short): the
     messages World.bcast_tensor sends.  Pure Python, no GPU"""
@@ -518,17 +502,7 @@ def bulk_fragments(nbytes, bulk_max):
 def send_bulk_check(origins, stride, n_ranks, bulk_max, lens=None, rank_stride=0, src=0x1000, dst=0x1000, flags=0):
     """rlo_send_bulk_check: the argument checks of the bulk send program that need no GPU; returns RLO_OK or
     RLO_E_INVAL (src / dst: pointers as integers, never dereferenced)"""
-    origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
-    ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
-    if ln is not None and ln.size != origin.size:
-        raise ValueError("send_bulk_check: %d lengths for %d messages" % (ln.size, origin.size))
-    cfg = L.SendBulkCfg()
-    cfg.k = int(origin.size)
-    cfg.origin = origin.ctypes.data if origin.size else None
-    cfg.len = None if ln is None or not ln.size else ln.ctypes.data
-    cfg.src, cfg.dst = src, dst
-    cfg.stride, cfg.rank_stride = stride, rank_stride
-    cfg.flags = flags
+    cfg, _keep = _send_cfg("send_bulk", origins, src, dst, stride, lens, rank_stride, 0, flags, 0)
     return L.load().rlo_send_bulk_check(ctypes.byref(cfg), n_ranks, bulk_max)
 
 
@@ -536,17 +510,7 @@ def send_storm_check(origins, slot, n_ranks, max_payload, lens=None, rank_stride
                      flags=0):
     """rlo_send_storm_check: the argument checks of the storm send program that need no GPU; returns RLO_OK or
     RLO_E_INVAL (src / dst: pointers as integers, never dereferenced)"""
-    origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
-    ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
-    if ln is not None and ln.size != origin.size:
-        raise ValueError("send_storm_check: %d lengths for %d messages" % (ln.size, origin.size))
-    cfg = L.SendStormCfg()
-    cfg.k = int(origin.size)
-    cfg.origin = origin.ctypes.data if origin.size else None
-    cfg.len = None if ln is None or not ln.size else ln.ctypes.data
-    cfg.src, cfg.dst = src, dst
-    cfg.slot, cfg.window, cfg.rank_stride = slot, window, rank_stride
-    cfg.flags = flags
+    cfg, _keep = _send_cfg("send_storm", origins, src, dst, slot, lens, rank_stride, window, flags, 0)
     return L.load().rlo_send_storm_check(ctypes.byref(cfg), n_ranks, max_payload)
 
 

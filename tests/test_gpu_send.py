@@ -4,71 +4,16 @@ memory -- on the hop kernel, open loop and ordered, in one part and several, and
 
 Expected values never come from the engine: payload bytes are this file's seeded NumPy source, tree parents
 pyoracle.tree, checksums pyoracle.msg_checksum summed over what a rank must receive, counts k minus the rank's own."""
-import re
+import functools
 
 import numpy as np
 import pytest
 
 import pyoracle as orc
+from send_cases import FILL, TAG_BCAST, check, forge_bus, gen, latency_runs_clean, rlo  # noqa: F401  (rlo: the fixture)
 
 pytestmark = pytest.mark.gpu
-FILL = 0xA5
-TAG_BCAST = 0
-MASK64 = (1 << 64) - 1
-
-
-@pytest.fixture(scope="module")
-def rlo():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import rlo as _rlo
-
-    return _rlo
-
-
-def _gen(n, slot, k, seed, origins=None):
-    """a seeded workload: origins (any rank, any mix), lengths from {1, 15, 16, 17, slot - 1, slot} within [1, slot],
-    and k x slot source bytes"""
-    rng = np.random.default_rng(seed)
-    if origins is None:
-        origins = rng.integers(0, n, k)
-    origins = np.asarray(origins, dtype=np.int32)
-    choices = sorted({x for x in (1, 15, 16, 17, slot - 1, slot) if 1 <= x <= slot})
-    lens = rng.choice(choices, len(origins)).astype(np.uint32)
-    src = rng.integers(0, 256, (len(origins), slot), dtype=np.uint8)
-    return origins, lens, src
-
-
-def _expected(n, origins, lens, src):
-    """(dst bytes [n][k][slot], deliveries [n], originated [n], checksum [n]) a correct run leaves"""
-    k, slot = src.shape
-    col = np.arange(slot)[None, :]
-    ln = lens.astype(np.int64)[:, None]
-    msg = np.where(col < ln, src, np.where(col < (ln + 15) // 16 * 16, 0, FILL)).astype(np.uint8)
-    want = np.broadcast_to(msg, (n, k, slot)).copy()
-    want[origins, np.arange(k)] = FILL  # the origin's own place is not written
-    cs = [orc.msg_checksum(int(origins[i]), i, TAG_BCAST, bytes(src[i, :lens[i]])) for i in range(k)]
-    total = sum(cs) & MASK64
-    own_sum = [0] * n
-    for i in range(k):
-        own_sum[origins[i]] += cs[i]
-    sums = np.array([(total - own_sum[r]) & MASK64 for r in range(n)], dtype=np.uint64)
-    own = np.bincount(origins, minlength=n)
-    return want, k - own, own, sums
-
-
-def _check(st, got, n, origins, lens, src):
-    want, cnt, own, sums = _expected(n, origins, lens, src)
-    assert (st["error"] == 0).all(), (st["error"], st["error_aux"])
-    assert np.array_equal(st["bcast_delivered"].astype(np.int64), cnt)
-    assert np.array_equal(st["originated"].astype(np.int64), own)
-    if not np.array_equal(got, want):
-        r, i, b = (int(x[0]) for x in np.nonzero(got != want))
-        raise AssertionError("rank %d message %d (origin %d, len %d) byte %d: got 0x%02x, want 0x%02x; %d bytes differ" %
-                             (r, i, origins[i], lens[i], b, got[r, i, b], want[r, i, b], int((got != want).sum())))
-    assert np.array_equal(st["bcast_sum"], sums)
+_gen = functools.partial(gen, storm=False)
 
 
 def _launch(w, origins, lens, src, dst=None, **kw):
@@ -106,7 +51,7 @@ def test_exact_bytes_open_loop(rlo, n, slot, k):
             if n == 300 and str(e).startswith("rlo_run failed") and "[-1]" in str(e):  # (RLO_E_INVAL from the launch itself)
                 pytest.skip("300 rank-waves of the send program are not co-resident on this device: the launch was refused")
             raise
-        _check(st, got, n, origins, lens, src)
+        check(st, got, n, origins, lens, src)
 
 
 @pytest.mark.parametrize("n", [8, 13, 64])
@@ -116,7 +61,7 @@ def test_trees_and_per_origin_fifo(rlo, n):
     parent = {o: orc.tree(n, o)[0] for o in range(n)}
     with rlo.World(n, max_payload=slot) as w:
         st, got = _launch(w, origins, lens, src, log=True, log_cap=k)
-        _check(st, got, n, origins, lens, src)
+        check(st, got, n, origins, lens, src)
         for r in range(n):
             rows = w.log(r, cap=k)
             assert len(rows) == k - int((origins == r).sum())
@@ -148,7 +93,7 @@ def test_back_pressure_and_ring_wrap(rlo, pattern):
     with rlo.World(n, max_payload=slot, ring_slots=cap) as w:
         assert w.info["ring_slots"] == cap
         st, got = _launch(w, origins, lens, src)
-        _check(st, got, n, origins, lens, src)
+        check(st, got, n, origins, lens, src)
 
 
 @pytest.mark.parametrize("n", [8, 64])
@@ -157,7 +102,7 @@ def test_ordered(rlo, n):
     origins, lens, src = _gen(n, slot, k, 4000 + n)
     with rlo.World(n, max_payload=slot) as w:
         st, got = _launch(w, origins, lens, src, ordered=True, log=True, log_cap=k)
-        _check(st, got, n, origins, lens, src)
+        check(st, got, n, origins, lens, src)
         for r in range(n):
             ids = [row[4] for row in w.log(r, cap=k)]
             assert ids == sorted(set(ids)) and len(ids) == k - int((origins == r).sum())  # strictly ascending: a total order
@@ -176,13 +121,7 @@ def test_three_launches_of_one_world(rlo):
         for j, k in enumerate((40, 96, 24)):  # (the last one into a buffer the second filled: re-filled by _launch)
             origins, lens, src = _gen(n, slot, k, 5000 + j)
             st, got = _launch(w, origins, lens, src, dst=dst, ordered=(j == 1))
-            _check(st, got, n, origins, lens, src)
-
-
-def _forge_bus(blob):
-    m = re.search(rb"[0-9a-fA-F]{4}:[0-9a-fA-F]{2}:[0-9a-fA-F]{2}\.[0-9]", blob)
-    assert m, "no PCI bus id in the exported blob"
-    return blob[:m.start()] + b"ffff:ff:1f.7" + blob[m.end():]
+            check(st, got, n, origins, lens, src)
 
 
 @pytest.mark.parametrize("forged", [False, True], ids=["agent", "system"])
@@ -196,7 +135,7 @@ def test_parts(rlo, n, bounds, forged):
     origins, lens, src = _gen(n, slot, k, 6000 + n)
 
     def forge(p, blobs):
-        return [b if q == p else _forge_bus(b) for q, b in enumerate(blobs)]
+        return [b if q == p else forge_bus(b) for q, b in enumerate(blobs)]
 
     spec = {"kind": "send", "origins": origins, "lens": lens, "slot": slot, "src": src}
     (st, _, _), rcs = sharded.run_inprocess(n, bounds, spec, max_payload=slot, uncached=forged,
@@ -204,14 +143,7 @@ def test_parts(rlo, n, bounds, forged):
     assert rcs == [0, 0], (st["error"], st["error_aux"])
     assert (st["part_last_kernel"] == 1).all()
     assert (st["part_sys_scope"] == (1 if forged else 0)).all()
-    _check(st, st["dst"], n, origins, lens, src)
-
-
-def _latency_runs_clean(w):
-    w.program_latency(16, 64)
-    w.run()
-    st = w.stats()
-    assert (st["error"] == 0).all() and int(st["originated"].sum()) == 16
+    check(st, st["dst"], n, origins, lens, src)
 
 
 def test_refusals(rlo):
@@ -225,16 +157,16 @@ def test_refusals(rlo):
     with rlo.World(n, max_payload=slot, one_xcd=True) as w:  # one-XCD worlds: refused at the program
         with pytest.raises(rlo.RloError):
             w.program_send(origins, s, d, slot, lens=lens)
-        _latency_runs_clean(w)
+        latency_runs_clean(w)
     with rlo.World(n, max_payload=slot, bulk_max=1 << 20) as w:  # a bulk world: the launch is refused
         w.program_send(origins, s, d, slot, lens=lens)
         with pytest.raises(rlo.RloError):
             w.run()
-        _latency_runs_clean(w)
+        latency_runs_clean(w)
     with rlo.World(n, max_payload=slot) as w:  # a slot above max_payload
         with pytest.raises(rlo.RloError):
             w.program_send(origins, torch.cat([s, s]), d, 128)
-        _latency_runs_clean(w)
+        latency_runs_clean(w)
         with pytest.raises(ValueError):  # extents and alignment are checked before the library sees them
             w.program_send(origins, s[:-16], d, slot)
         with pytest.raises(ValueError):

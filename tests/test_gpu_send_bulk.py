@@ -12,23 +12,11 @@ import numpy as np
 import pytest
 
 import pyoracle as orc
+from send_cases import FILL, MASK64, TAG_BCAST, rlo  # noqa: F401  (rlo: the fixture)
 
 pytestmark = pytest.mark.gpu
-FILL = 0xA5
-TAG_BCAST, TAG_BULK = 0, 10
-MASK64 = (1 << 64) - 1
+TAG_BULK = 10
 KIB, MIB = 1 << 10, 1 << 20
-
-
-@pytest.fixture(scope="module")
-def rlo():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import rlo as _rlo
-
-    return _rlo
 
 
 def _source(k, stride, seed):

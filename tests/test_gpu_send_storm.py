@@ -7,76 +7,16 @@ World.bcast_rows.
 Expected values never come from the engine: payload bytes are this file's seeded NumPy source, tree parents
 pyoracle.tree, checksums pyoracle.msg_checksum summed over what a rank must receive, counts k minus the rank's own.
 dst is pre-filled with 0xA5, so the bytes that must stay unwritten are checked too."""
-import re
+import functools
 
 import numpy as np
 import pytest
 
 import pyoracle as orc
+from send_cases import FILL, TAG_BCAST, check, forge_bus, gen, latency_runs_clean, rlo  # noqa: F401  (rlo: the fixture)
 
 pytestmark = pytest.mark.gpu
-FILL = 0xA5
-TAG_BCAST = 0
-MASK64 = (1 << 64) - 1
-
-
-@pytest.fixture(scope="module")
-def rlo():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import rlo as _rlo
-
-    return _rlo
-
-
-def _gen(n, slot, k, seed, origins=None):
-    """a seeded workload: origins (all ranks, a random mix), lengths from {1, 15, 16, 17, slot - 1, slot} -- large
-    slots add {64, 65, 368, 369, 1008, 1024, 1025}: the staged 5 chunks, the small copy path's 24 chunks, the hop
-    kernel's limit -- within [1, slot], and k x slot source bytes"""
-    rng = np.random.default_rng(seed)
-    if origins is None:
-        origins = rng.integers(0, n, k)
-    origins = np.asarray(origins, dtype=np.int32)
-    pool = {1, 15, 16, 17, slot - 1, slot}
-    if slot > 112:
-        pool |= {64, 65, 368, 369, 1008, 1024, 1025}
-    choices = sorted(x for x in pool if 1 <= x <= slot)
-    lens = rng.choice(choices, len(origins)).astype(np.uint32)
-    lens[:len(choices)] = choices[:len(origins)]  # every boundary at least once
-    src = rng.integers(0, 256, (len(origins), slot), dtype=np.uint8)
-    return origins, lens, src
-
-
-def _expected(n, origins, lens, src):
-    """(dst bytes [n][k][slot], deliveries [n], originated [n], checksum [n]) a correct run leaves"""
-    k, slot = src.shape
-    col = np.arange(slot)[None, :]
-    ln = lens.astype(np.int64)[:, None]
-    msg = np.where(col < ln, src, np.where(col < (ln + 15) // 16 * 16, 0, FILL)).astype(np.uint8)
-    want = np.broadcast_to(msg, (n, k, slot)).copy()
-    want[origins, np.arange(k)] = FILL  # the origin's own place is not written
-    cs = [orc.msg_checksum(int(origins[i]), i, TAG_BCAST, bytes(src[i, :lens[i]])) for i in range(k)]
-    total = sum(cs) & MASK64
-    own_sum = [0] * n
-    for i in range(k):
-        own_sum[origins[i]] += cs[i]
-    sums = np.array([(total - own_sum[r]) & MASK64 for r in range(n)], dtype=np.uint64)
-    own = np.bincount(origins, minlength=n)
-    return want, k - own, own, sums
-
-
-def _check(st, got, n, origins, lens, src):
-    want, cnt, own, sums = _expected(n, origins, lens, src)
-    assert (st["error"] == 0).all(), (st["error"], st["error_aux"])
-    assert np.array_equal(st["bcast_delivered"].astype(np.int64), cnt)
-    assert np.array_equal(st["originated"].astype(np.int64), own)
-    if not np.array_equal(got, want):
-        r, i, b = (int(x[0]) for x in np.nonzero(got != want))
-        raise AssertionError("rank %d message %d (origin %d, len %d) byte %d: got 0x%02x, want 0x%02x; %d bytes differ" %
-                             (r, i, origins[i], lens[i], b, got[r, i, b], want[r, i, b], int((got != want).sum())))
-    assert np.array_equal(st["bcast_sum"], sums)
+_gen = functools.partial(gen, storm=True)
 
 
 def _launch(w, origins, lens, src, rank_stride=0, **kw):
@@ -120,7 +60,7 @@ def test_exact_bytes(rlo, n, mp, k, waves):
             if n == 300 and str(e).startswith("rlo_run failed") and "[-1]" in str(e):  # (RLO_E_INVAL from the launch itself)
                 pytest.skip("300 rank-workgroups are not co-resident on this device: the launch was refused")
             raise
-        _check(st, got.reshape(n, k, mp), n, origins, lens, src)
+        check(st, got.reshape(n, k, mp), n, origins, lens, src)
         if mp >= 4096:
             assert w.info["pull"] == 1  # pulled payloads: the default of large-slot worlds
 
@@ -136,7 +76,7 @@ def test_ring_wrap_and_refused_admissions(rlo, org):
     with rlo.World(n, max_payload=slot, ring_slots=cap) as w:
         assert w.info["ring_slots"] == cap
         st, got = _launch(w, origins, lens, src)
-        _check(st, got.reshape(n, len(origins), slot), n, origins, lens, src)
+        check(st, got.reshape(n, len(origins), slot), n, origins, lens, src)
 
 
 @pytest.mark.parametrize("n,mp", [(8, 64), (13, 64), (64, 64), (8, 4096)], ids=lambda v: str(v))
@@ -146,7 +86,7 @@ def test_trees_and_per_origin_fifo(rlo, n, mp):
     parent = {o: orc.tree(n, o)[0] for o in range(n)}
     with rlo.World(n, max_payload=mp) as w:
         st, got = _launch(w, origins, lens, src, log=True, log_cap=k)
-        _check(st, got.reshape(n, k, mp), n, origins, lens, src)
+        check(st, got.reshape(n, k, mp), n, origins, lens, src)
         for r in range(n):
             rows = w.log(r, cap=k)
             assert len(rows) == k - int((origins == r).sum())
@@ -167,7 +107,7 @@ def test_pushed_large_payloads(rlo, monkeypatch):
     with rlo.World(n, max_payload=mp) as w:
         assert w.info["pull"] == 0
         st, got = _launch(w, origins, lens, src)
-        _check(st, got.reshape(n, k, mp), n, origins, lens, src)
+        check(st, got.reshape(n, k, mp), n, origins, lens, src)
 
 
 def test_three_launches_then_other_programs(rlo):
@@ -178,7 +118,7 @@ def test_three_launches_then_other_programs(rlo):
         for j, k in enumerate((40, 96, 24)):
             origins, lens, src = _gen(n, slot, k, 5000 + j)
             st, got = _launch(w, origins, lens, src)
-            _check(st, got.reshape(n, k, slot), n, origins, lens, src)
+            check(st, got.reshape(n, k, slot), n, origins, lens, src)
         ks, ln, seed = 128, 64, 11
         w.program_storm(ks, ln, seed=seed)
         w.run()
@@ -197,7 +137,7 @@ def test_three_launches_then_other_programs(rlo):
         w.program_send(origins, s, d, slot, lens=lens)
         w.run()
         assert w.info_now()["last_kernel"] == 1
-        _check(w.stats(), d.cpu().numpy().reshape(n, k, slot), n, origins, lens, src)
+        check(w.stats(), d.cpu().numpy().reshape(n, k, slot), n, origins, lens, src)
 
 
 def test_rank_stride_gap_stays_unwritten(rlo):
@@ -207,13 +147,7 @@ def test_rank_stride_gap_stays_unwritten(rlo):
     with rlo.World(n, max_payload=slot) as w:
         st, got = _launch(w, origins, lens, src, rank_stride=rs)
         assert (got[:, k * slot:] == FILL).all()  # the gap up to rank_stride
-        _check(st, got[:, :k * slot].reshape(n, k, slot), n, origins, lens, src)
-
-
-def _forge_bus(blob):
-    m = re.search(rb"[0-9a-fA-F]{4}:[0-9a-fA-F]{2}:[0-9a-fA-F]{2}\.[0-9]", blob)
-    assert m, "no PCI bus id in the exported blob"
-    return blob[:m.start()] + b"ffff:ff:1f.7" + blob[m.end():]
+        check(st, got[:, :k * slot].reshape(n, k, slot), n, origins, lens, src)
 
 
 @pytest.mark.parametrize("forged", [False, True], ids=["agent", "system"])
@@ -227,7 +161,7 @@ def test_parts(rlo, forged):
     origins, lens, src = _gen(n, slot, k, 6000 + n)
 
     def forge(p, blobs):
-        return [b if q == p else _forge_bus(b) for q, b in enumerate(blobs)]
+        return [b if q == p else forge_bus(b) for q, b in enumerate(blobs)]
 
     spec = {"kind": "send_storm", "origins": origins, "lens": lens, "slot": slot, "src": src}
     (st, _, _), rcs = sharded.run_inprocess(n, bounds, spec, max_payload=slot, uncached=forged,
@@ -235,14 +169,7 @@ def test_parts(rlo, forged):
     assert rcs == [0, 0], (st["error"], st["error_aux"])
     assert (st["part_last_kernel"] == 0).all()
     assert (st["part_sys_scope"] == (1 if forged else 0)).all()
-    _check(st, st["dst"], n, origins, lens, src)
-
-
-def _latency_runs_clean(w):
-    w.program_latency(16, 64)
-    w.run()
-    st = w.stats()
-    assert (st["error"] == 0).all() and int(st["originated"].sum()) == 16
+    check(st, st["dst"], n, origins, lens, src)
 
 
 def test_refusals(rlo):
@@ -255,19 +182,19 @@ def test_refusals(rlo):
     torch.cuda.synchronize()
     inval = r"rlo_program_send_storm failed.*\[-1\]"  # RLO_E_INVAL from the program call, before anything is uploaded
     with rlo.World(n, max_payload=slot, bulk_max=1 << 20) as w:  # a bulk world
-        _latency_runs_clean(w)
+        latency_runs_clean(w)
         with pytest.raises(rlo.RloError, match=inval):
             w.program_send_storm(origins, s, d, slot, lens=lens)
         w.run()  # the previous program still runs
         assert (w.stats()["error"] == 0).all() and int(w.stats()["originated"].sum()) == 16
     with rlo.World(n, max_payload=slot, one_xcd=True) as w:  # a one-XCD world
-        _latency_runs_clean(w)
+        latency_runs_clean(w)
         with pytest.raises(rlo.RloError, match=inval):
             w.program_send_storm(origins, s, d, slot, lens=lens)
         w.run()
         assert (w.stats()["error"] == 0).all() and int(w.stats()["originated"].sum()) == 16
     with rlo.World(n, max_payload=slot) as w:  # a slot beyond max_payload
-        _latency_runs_clean(w)
+        latency_runs_clean(w)
         with pytest.raises(rlo.RloError, match=inval):
             w.program_send_storm(origins, torch.cat([s, s]), d, 128)
         w.run()

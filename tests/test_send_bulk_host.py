@@ -2,15 +2,11 @@
 that need no GPU), the rlo_send_bulk_cfg_t mirror, rlo.bulk_fragments (the fragmentation World.bcast_tensor uses in a
 world with bulk messages), and the kernel pick of the program's mode."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
 import test_kernel_pick as kp
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(REPO, "include")
 MIB = 1 << 20
 SENDB = 2097152  # rlo_device.hpp MODE_SENDB
 P_SENDB = 0xFFFFFFFF & ~(kp.STORM | kp.IAR | kp.HOST | 32768 | 65536)  # rlo_kernel.hip kPmSendBulk
@@ -72,25 +68,6 @@ def test_check_null_cfg_and_count():
     cfg.origin = ctypes.addressof(org)
     assert lib.rlo_send_bulk_check(ctypes.byref(cfg), 8, MIB) == L.RLO_OK
     assert lib.rlo_send_bulk_check(ctypes.byref(cfg), 0, MIB) == L.RLO_E_INVAL
-
-
-def test_send_bulk_cfg_matches_the_c_header(tmp_path):
-    """sizeof and every field offset of rlo_send_bulk_cfg_t against L.SendBulkCfg"""
-    from rlo import _lib as L
-
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rlo_hip.h"', 'int main(void) {',
-             'printf("sizeof %zu\\n", sizeof(rlo_send_bulk_cfg_t));']
-    for fname, _ in L.SendBulkCfg._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(rlo_send_bulk_cfg_t, %s));' % (fname, fname))
-    lines += ['return 0;', '}']
-    src = tmp_path / "send_bulk_sizes.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "send_bulk_sizes"
-    subprocess.run(["gcc", "-I", INCLUDE, str(src), "-o", str(exe)], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["sizeof"]) == ctypes.sizeof(L.SendBulkCfg) == 64
-    for fname, _ in L.SendBulkCfg._fields_:
-        assert int(got[fname]) == getattr(L.SendBulkCfg, fname).offset, fname
 
 
 @pytest.mark.parametrize("bulk_max", [MIB, MIB + 16, MIB + 5, 48])

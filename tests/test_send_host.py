@@ -2,10 +2,11 @@
 GPU), the rlo_send_cfg_t mirror, and rlo.send_fragments (the fragmentation World.bcast_tensor uses)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+from send_cases import header_layout
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(REPO, "include")
@@ -67,24 +68,19 @@ def test_send_check_null_cfg():
     assert L.load().rlo_send_check(None, 8, 64) == L.RLO_E_INVAL
 
 
-def test_send_cfg_matches_the_c_header(tmp_path):
-    """sizeof and every field offset of rlo_send_cfg_t against L.SendCfg, and the flag's value"""
+@pytest.mark.parametrize("cname,mirror", [("rlo_send_cfg_t", "SendCfg"), ("rlo_send_bulk_cfg_t", "SendBulkCfg"),
+                                          ("rlo_send_storm_cfg_t", "SendStormCfg")])
+def test_send_cfgs_match_the_c_header(tmp_path, cname, mirror):
+    """sizeof and every field offset of the three send cfgs against their ctypes mirrors, and the flag's value"""
     from rlo import _lib as L
 
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rlo_hip.h"', 'int main(void) {',
-             'printf("sizeof %zu\\n", sizeof(rlo_send_cfg_t));', 'printf("ordered %u\\n", RLO_SEND_ORDERED);']
-    for fname, _ in L.SendCfg._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(rlo_send_cfg_t, %s));' % (fname, fname))
-    lines += ['return 0;', '}']
-    src = tmp_path / "send_sizes.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "send_sizes"
-    subprocess.run(["gcc", "-I", INCLUDE, str(src), "-o", str(exe)], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["sizeof"]) == ctypes.sizeof(L.SendCfg)
-    assert int(got["ordered"]) == L.RLO_SEND_ORDERED
-    for fname, _ in L.SendCfg._fields_:
-        assert int(got[fname]) == getattr(L.SendCfg, fname).offset, fname
+    py = getattr(L, mirror)
+    got = header_layout(tmp_path, cname, py, macros=["RLO_SEND_ORDERED"])
+    assert got["RLO_SEND_ORDERED"] == L.RLO_SEND_ORDERED
+    if mirror != "SendCfg":
+        assert got["sizeof"] == 64
+    if mirror == "SendStormCfg":
+        assert [f for f, _ in py._fields_] == ["k", "origin", "len", "src", "dst", "slot", "window", "rank_stride", "flags", "log_cap"]
 
 
 def test_device_error_names_cover_the_header():

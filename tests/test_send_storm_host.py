@@ -3,15 +3,11 @@ rlo_program_send_storm that need no GPU), the rlo_send_storm_cfg_t mirror, the k
 rlo.rows_slot (the row and padding arithmetic of World.bcast_rows)."""
 import ctypes
 import itertools
-import os
-import subprocess
 
 import pytest
 
 import test_kernel_pick as kp
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(REPO, "include")
 SENDS, SENDB, SEND, TL, HDIAG = 8388608, 2097152, 1048576, 32768, 4096  # rlo_device.hpp MODE_SENDS, _SENDB, _SEND, _TL, _HDIAG
 # rlo_kernel.hip kPmStormSend
 P_SENDS = 0xFFFFFFFF & ~(kp.LAT | kp.IAR | kp.HOST | TL | kp.LL | SEND | SENDB | HDIAG)
@@ -73,26 +69,6 @@ def test_check_null_cfg_and_count():
     assert lib.rlo_send_storm_check(ctypes.byref(cfg), 8, 64) == L.RLO_OK
     with pytest.raises(ValueError):
         _check(lens=[1, 2, 3])  # the wrapper: one length per message
-
-
-def test_ctypes_struct_matches_the_c_header(tmp_path):
-    from rlo import _lib as L
-
-    cname, py = "rlo_send_storm_cfg_t", L.SendStormCfg
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rlo_hip.h"', 'int main(void) {',
-             'printf("%s %%zu\\n", sizeof(%s));' % (cname, cname)]
-    for fname, _ in py._fields_:
-        lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, fname, cname, fname))
-    lines += ['return 0;', '}']
-    src = tmp_path / "sizes.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "sizes"
-    subprocess.run(["gcc", "-I", INCLUDE, str(src), "-o", str(exe)], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got[cname]) == ctypes.sizeof(py) == 64
-    assert [f for f, _ in py._fields_] == ["k", "origin", "len", "src", "dst", "slot", "window", "rank_stride", "flags", "log_cap"]
-    for fname, _ in py._fields_:
-        assert int(got["%s.%s" % (cname, fname)]) == getattr(py, fname).offset, fname
 
 
 def test_pick_of_the_new_bit_alone():
