@@ -21,6 +21,9 @@
  *             memory, every receiver's copy written to a destination buffer in device memory (the hop kernel only)
  *   send_bulk: the same interface for LARGE buffers, in a world with bulk messages: k closed-loop bcasts of up to
  *             bulk_max bytes each, read from and written to caller-owned device memory by the mover workgroups
+ *   decide  : iar rounds on caller-owned device buffers: proposal data read from a source buffer in device memory,
+ *             each rank's verdicts from a table in device memory, the data every judging rank received and every
+ *             rank's decisions written to device memory (the hop kernel only, worlds of <= 16 ranks)
  *   host    : the host-service program under the drop-in rootless_ops.h (commands and pickups in host memory)
  */
 #ifndef RLO_HIP_H
@@ -358,6 +361,52 @@ typedef struct {
 int rlo_program_iar(rlo_world_t* w, const rlo_iar_cfg_t* cfg, int64_t nprop, const int32_t* origin, const int32_t* pid,
                     const uint8_t* data, const uint32_t* data_off, const uint32_t* data_len);
 
+/* decide: proposal / vote / decision rounds on CALLER-OWNED DEVICE BUFFERS.  k proposals; proposal i is submitted by
+ * rank origin[i] with pid = i (the 64-bit data_len of its PBuf frame untouched), each rank submitting its own in list
+ * order, one in flight at a time (pool 1: the reference's my_own_proposal, rootless_ops.c:241).  The protocol is the
+ * iar program's, unchanged -- trees, per-edge FIFO, votes, the decision bcast, the originator's final judge(NULL) that
+ * every device judge approves; only the sources and sinks differ:
+ *   data     : the origin's rank-wave reads proposal i's len[i] bytes (0 .. slot) from src + i * slot;
+ *   judge    : local rank lr declines proposal i iff verdict[lr * k + i] == 0 (any non-zero byte approves), the byte
+ *              read when the proposal reaches that rank; the origin's own entry is never read; verdict == NULL
+ *              approves everything;
+ *   received : a rank that judges proposal i (whatever its verdict) writes the data chunks it holds to
+ *              dst + (lr * k + i) * slot: bytes [0, len) are the source's, [len, round16(len)) zero (the message's last
+ *              16-B chunk as it travels), the rest of the place is not written; a rank a declined proposal never
+ *              reached writes nothing, and the origin's own place is never written.  So for every proposal decided 1
+ *              every non-origin rank's place holds the data;
+ *   decision : every rank writes decision[lr * k + i] = 1 (approved) or 0 (declined) -- a receiver when the decision
+ *              message is delivered, the origin when its own proposal is decided.  After a clean launch every byte of
+ *              decision is 0 or 1 and all ranks' rows are equal.
+ * No byte of data, verdict or decision crosses the host.  rlo_stats: the iar program's counters.  RLO_FLAG_LOG: the iar
+ * program's judge / action / decision / result records.
+ * The hop kernel (rlo_hop.hip) alone runs it.  RLO_E_INVAL, before anything is uploaded or reset: any argument outside
+ * the ranges below, a world of more than 16 ranks, a world with bulk messages, a RLO_PART_ONE_XCD world (for
+ * rlo_program_send's reason), a world whose pending table is in HBM (RLO_PART_PEND_HBM).  A launch that cannot run the
+ * hop kernel (rank-waves not co-resident, a diagnostics mode that forces the progress kernel) returns RLO_E_INVAL
+ * before anything is reset, never the progress kernel.  On the device a proposal or decision with id >= k, or a
+ * proposal with more than slot bytes of data, raises RLO_DERR_BAD_SLOT: consumed, not forwarded, nothing stored to
+ * caller memory.  Worlds of several parts (one process or several): each part passes its own src, verdict, dst and
+ * decision; a part reads only its own ranks' proposals from src. */
+typedef struct {
+    int64_t k;              /* proposals, 1 .. 2^31-1                                                                */
+    const int32_t* origin;  /* host [k]: the rank that submits proposal i                                            */
+    const uint32_t* len;    /* host [k]: data bytes of proposal i, 0 .. slot; NULL = every proposal is `slot` bytes   */
+    const void* src;        /* DEVICE, 16-B aligned, k * slot bytes: proposal i's data at i * slot.  Must not change
+                               while the launch runs                                                               */
+    const uint8_t* verdict; /* DEVICE, n_local * k bytes, or NULL (approve everything)                              */
+    void* dst;              /* DEVICE, 16-B aligned, n_local * k * slot bytes                                        */
+    uint8_t* decision;      /* DEVICE, n_local * k bytes                                                             */
+    uint32_t slot;          /* bytes per proposal place: a multiple of 16, 16 .. 992 (the slot header chunk, the PBuf
+                               header chunk and 62 data chunks = the hop kernel's 64 lanes), and 16 + slot <= the
+                               world's max_payload rounded up to 16                                                */
+    uint32_t flags;         /* RLO_FLAG_LOG                                                                          */
+    uint32_t log_cap, pad;
+} rlo_decide_cfg_t;
+int rlo_program_decide(rlo_world_t* w, const rlo_decide_cfg_t* cfg);
+/* the argument checks of rlo_program_decide that need no GPU (pure host): RLO_OK or RLO_E_INVAL */
+int rlo_decide_check(const rlo_decide_cfg_t* cfg, int n_ranks, uint32_t max_payload);
+
 /* one event record (parity log / host pickup ring).  A bulk delivery (kind 1 | 10 << 8) logs
  * len = message bytes and, once its VERIFY job ran, aux | payload_idx << 32 = the message checksum
  * (the oracle's orc_msg_checksum) */
@@ -466,10 +515,13 @@ int rlo_storm_lengths(uint64_t seed, uint64_t k, uint32_t len, uint32_t len_max,
  * kernel: 0 the progress kernel, 1 the hop kernel (as rlo_world_info_t.last_kernel); variant: 8 / 4 waves, 5 = 4 waves
  * with bulk messages (progress only); mode: the launch's mode bits (rlo_device.hpp Mode); pend_hbm, sys_scope: as
  * rlo_world_info_t.  out: the instantiation's template arguments -- progress {W, BULK, LL, PH, program mask}, hop
- * {PH, SYS, LOC, SEND, 0}.  RLO_E_INVAL: no such kernel (the hop kernel's send program, or system scope, on one XCD;
+ * {PH, SYS, LOC, SEND, DECIDE} (DECIDE: 1 for the decide program's rows -- mode MODE_DECIDE | MODE_IAR | MODE_LL --, 0
+ * for every other).  RLO_E_INVAL: no such kernel (the hop kernel's send program, or system scope, on one XCD; the hop
+ * kernel's decide program on one XCD, with the send program's bit or with a pending table in HBM;
  * the bulk send program -- mode MODE_SENDB | MODE_LL, no other program bit -- anywhere but variant 5 with doorbells;
  * the storm send program -- mode MODE_SENDS, no other program bit and no doorbells: the storm-send instantiation of
- * variant 8 or 4 -- on variant 5).  Beside a program bit (storm, latency, iar, host) neither send bit changes the pick */
+ * variant 8 or 4 -- on variant 5).  Beside a program bit (storm, latency, iar, host) neither send bit changes the pick, and
+ * the progress kernel's pick ignores MODE_DECIDE */
 int rlo_kernel_pick(int kernel, int variant, uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]);
 /* introspection (no GPU): the forwarding tables the storm kernel fills for rank `rank` of an n-rank world, by the
  * function the kernel itself calls.  below[o] / above[o]: the out-rings a message of origin o goes to when it came

@@ -83,6 +83,9 @@ enum Mode : uint32_t {
                             //   caller-owned device buffers at storm rate; the kernel runs it with MODE_STORM set too
     MODE_NOPIPE = 16777216u,  // diagnostics build, A/B and test: the 8-wave storm kernel's iteration in its serial order (every
                               //   wave copies, then wave 0 alone consumes, polls and selects) instead of the pipelined one
+    MODE_DECIDE = 33554432u,  // the decide program (rlo_hop.hip, the DECIDE instantiations only; always beside MODE_IAR |
+                              //   MODE_LL): iar rounds whose proposal data, verdicts, received data and decisions are the
+                              //   caller's device buffers.  The progress kernel has no such program and ignores the bit
     MODE_CORRUPT = 65536u,  // diagnostics build, test of the VERIFY check: a direct scatter zeroes one granule of one copy
     MODE_HOST = 128u,  // host-service: originations / judge verdicts come from a host command ring,
                        //   deliveries / judge requests / results go to a host pickup ring (rootless_ops.h)
@@ -323,6 +326,13 @@ struct Params {
     // sched_len runs beside sched_ids.  Message i's bytes at send_src + i * send_slot, local rank lr's copy at
     // send_dst + lr * send_rank_stride + i * send_slot
     const uint32_t* sched_len;      // [sched_ids entries] bytes of each own message
+    // the decide program (MODE_DECIDE; appended likewise): the own lists are prop_off / prop_pid / prop_data_len (a
+    // proposal's pid is its index i; prop_data_off and prop_data are unused).  All four buffers are the caller's
+    const uint8_t* decide_src;      // DEVICE: proposal i's data at i * decide_slot
+    const uint8_t* decide_verdict;  // DEVICE [n_local][decide_k] or null (approve all): 0 = local rank lr declines proposal i
+    uint8_t* decide_dst;            // DEVICE: the data local rank lr judged of proposal i at (lr * decide_k + i) * decide_slot
+    uint8_t* decide_out;            // DEVICE [n_local][decide_k]: proposal i's decision (0 / 1) as local rank lr learnt it
+    uint32_t decide_k, decide_slot; // proposals; bytes per proposal place (a multiple of 16, <= 992)
 };
 
 // ---- bulk messages (longer than a ring slot; SURVEY §8(f)1, BASELINE configs[2], [4]).

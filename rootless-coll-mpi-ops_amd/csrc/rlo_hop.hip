@@ -83,10 +83,19 @@ enum HopCnt : int {
 // set beside it, the latency program's closed loop (RLO_SEND_ORDERED).  No pending table, no one-XCD form: instantiated
 // for the two scopes only (RLO_HOP_ROWS at the end of this file); every statement of it sits under
 // `if constexpr (SEND)`, so the other instantiations are what they were
+//
+// DECIDE (MODE_DECIDE beside MODE_IAR, rlo_program_decide): the decide program -- the iar program with the caller's
+// device buffers at its sources and sinks.  Proposal i (pid = i) carries the data its origin's
+// rank-wave reads from decide_src; the judge is the caller's table decide_verdict (a zero byte declines); a rank that
+// judges a proposal writes the data chunks it holds to its place in decide_dst, and every rank writes each decision it
+// learns to decide_out.  The protocol -- trees, FIFO, votes, the decision bcast -- is the iar program's, untouched.
+// Pending table in LDS, no one-XCD form: instantiated for the two scopes only; every statement of it sits under
+// `if constexpr (DECIDE)`, so the other instantiations are what they were
 constexpr uint32_t kSendBurst = 4;  // open loop: originations per round at most, so taking ring messages is never starved
-template <bool PH, bool SYS, bool LOC, bool SEND = false>
+template <bool PH, bool SYS, bool LOC, bool SEND = false, bool DECIDE = false>
 __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
     static_assert(!SEND || (!PH && !LOC), "the send program has no pending table and no one-XCD form");
+    static_assert(!DECIDE || (!PH && !LOC && !SEND), "the decide program: pending table in LDS, no one-XCD form, no send");
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
     __shared__ HopShared S;
     if constexpr (LOC)
@@ -192,6 +201,15 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
         nx_dl_v = vld32(P.prop_data_len, (uint32_t)(poff + i));
         nx_doff_v = vld32(P.prop_data_off, (uint32_t)(poff + i));
         nx_stage = 1;
+    };
+    // the decide program: proposal pid's dl data bytes in the caller's source, as a resource that ends at round4(dl)
+    // (what the prefetch reads prop_data through); its places are 16-B aligned, so 16-B loads are the only path
+    auto decide_data = [&](uint32_t pid, uint32_t dl) -> __amdgpu_buffer_rsrc_t {
+        return mk_rsrc(const_cast<uint8_t*>(P.decide_src) + (uint64_t)pid * P.decide_slot, (dl + 3u) & ~3u);
+    };
+    // ... and local rank lr's entry for proposal id in a [n_local][decide_k] byte table of the caller's
+    auto decide_at = [&](const uint8_t* tab, uint32_t id) -> __attribute__((address_space(1))) uint8_t* {
+        return (__attribute__((address_space(1))) uint8_t*)(const_cast<uint8_t*>(tab) + (uint64_t)(uint32_t)lr * P.decide_k + id);
     };
     // the latency program: my originations
     uint32_t lat_pos = 0, lat_seen = 0;
@@ -381,6 +399,12 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
                 err(ERR_BAD_SLOT, w0);
                 return true;
             }
+        if constexpr (DECIDE)  // a message that names no place in the caller's buffers (this program has no bcasts)
+            if (tag == TAG_BCAST || id >= P.decide_k ||  // (a proposal's data_len: the message's and its PBuf frame's)
+                (tag == TAG_PROPOSAL && (len < 16u || len - 16u > P.decide_slot || rdl32(v.z, 1) > P.decide_slot))) {
+                err(ERR_BAD_SLOT, w0);
+                return true;
+            }
         int judge = 1;
         u32x4 pe = {0u, 0u, 0u, 0u};
         if (tag != TAG_BCAST) pe = pend_rd(origin, pseq);
@@ -390,7 +414,15 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
             // word 2 is data_len, the data from chunk 2 on (LDS copy of this lane's chunk)
             uint32_t dl = rdl32(v.z, 1);
             if (dl > len - 16u) dl = len > 16u ? len - 16u : 0u;
-            if (P.judge_kind == JUDGE_ISP) {
+            if constexpr (DECIDE) {
+                // the caller's table: this rank's byte for proposal id (id < decide_k: checked above), read now that the
+                // proposal is here -- a vector load through a resource over this rank's row; no table approves
+                if (P.decide_verdict) {
+                    const __amdgpu_buffer_rsrc_t rj =
+                        mk_rsrc(const_cast<uint8_t*>(P.decide_verdict) + (uint64_t)(uint32_t)lr * P.decide_k, P.decide_k);
+                    judge = __builtin_amdgcn_raw_buffer_load_b8(rj, id, 0, 0) != 0 ? 1 : 0;
+                }
+            } else if (P.judge_kind == JUDGE_ISP) {
                 if (q < nch) *reinterpret_cast<u32x4*>(S.vote + 16u * q) = v;  // (scratch: no vote staged now)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 const uint8_t* d = S.vote + kHdr + 16u;
@@ -467,6 +499,14 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
                 const uint32_t k = (uint32_t)g >> 1;
                 CNT_ADD(HC_JUDGE, 1);
                 if (logon && lane == 0) log_put<kPmHop>(S, P, lr, LOG_JUDGE, origin, from, id, len, judge, 0);
+                if constexpr (DECIDE) {
+                    // the data chunks this rank holds (whatever it judged) to its place for proposal id (id < decide_k,
+                    // len - 16 <= decide_slot: checked above).  The resource covers that place alone, so the hardware
+                    // drops whatever would fall outside it.  Ordinary stores, no hand-off: nothing in the launch reads dst
+                    const __amdgpu_buffer_rsrc_t rd =
+                        mk_rsrc(P.decide_dst + ((uint64_t)(uint32_t)lr * P.decide_k + id) * P.decide_slot, P.decide_slot);
+                    if (q >= 2u && q < nch) __builtin_amdgcn_raw_buffer_store_b128(v, rd, 16u * (q - 2u), 0, 0);
+                }
                 if (!judge) {  // declined: vote 0, not forwarded, not pending (:700-706)
                     vote_up(k, origin, (int32_t)id, pseq, 0);
                 } else {
@@ -486,6 +526,8 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
             CNT_ADD(HC_DEC, 1);
             if (vote != 0) CNT_ADD(HC_DEC_APPR, 1);
             if (logon && lane == 0) log_put<kPmHop>(S, P, lr, LOG_DELIVER | (TAG_DECISION << 8), origin, from, id, 7, vote, 0);
+            if constexpr (DECIDE)  // the decision as delivered here (id < decide_k: checked above): one byte, no hand-off
+                if (lane == 0) *decide_at(P.decide_out, id) = vote != 0 ? 1 : 0;
         }
         if constexpr (kHopProf) {
             const uint64_t tk3 = __builtin_amdgcn_s_memtime();
@@ -653,7 +695,10 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
             const uint32_t nch = (kHdr + 16u + nx_dl + 15u) >> 4;
             nx_v = u32x4{0u, 0u, 0u, 0u};
             if (lane == 1) nx_v = u32x4{(uint32_t)uni((int)nx_pid_v), 1u, nx_dl, 0u};  // PBuf [pid][vote=1][data_len u64] (:1369-1396)
-            if ((nx_doff & 3u) == 0u) {
+            if constexpr (DECIDE) {  // from the caller's source, exactly as from prop_data below (nx_doff is unused)
+                const __amdgpu_buffer_rsrc_t rd = decide_data((uint32_t)uni((int)nx_pid_v), nx_dl);
+                if (lane >= 2 && (uint32_t)lane < nch) nx_v = __builtin_amdgcn_raw_buffer_load_b128(rd, 16u * ((uint32_t)lane - 2u), 0, 0);
+            } else if ((nx_doff & 3u) == 0u) {
                 // dword-aligned data (the usual packing): 16-B loads, left in flight -- the bytes past data_len are
                 // masked off at the origination (the range of the resource ends at the data's end, rounded up)
                 const __amdgpu_buffer_rsrc_t rd = mk_rsrc(const_cast<uint8_t*>(P.prop_data) + nx_doff, (nx_dl + 3u) & ~3u);
@@ -797,6 +842,8 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
                 CNT_ADD(HC_OWN_DEC, 1);
                 if (dec) CNT_ADD(HC_OWN_APPR, 1);
                 if (logon && lane == 0) log_put<kPmHop>(S, P, lr, LOG_RESULT, me, -1, id, 0, (int)dec, (uint32_t)k);
+                if constexpr (DECIDE)  // my own proposal, decided (id: one of my own list, < decide_k)
+                    if (lane == 0) *decide_at(P.decide_out, id) = dec != 0 ? 1 : 0;
                 if (lane == k) { own_state_r = 0; own_pid_r = -1; }  // proposalPool_rm (:1334-1347) / RLO_proposal_reset (:1649-1673)
                 progressed = true;
             }
@@ -813,8 +860,15 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
                     dl = P.prop_data_len[pi];
                     const uint32_t nch = (kHdr + 16u + dl + 15u) >> 4;
                     if (lane == 1) pv = u32x4{id, 1u, dl, 0u};
-                    else if (lane >= 2 && (uint32_t)lane < nch)
-                        pv = gen_chunk(P, K_PROP, me, id, 16u + dl, (uint32_t)pi, 1, (uint32_t)lane);
+                    else if (lane >= 2 && (uint32_t)lane < nch) {
+                        if constexpr (DECIDE) {  // (the caller's source: whole dwords, the tail masked as below)
+                            pv = __builtin_amdgcn_raw_buffer_load_b128(decide_data(id, dl), 16u * ((uint32_t)lane - 2u), 0, 0);
+                            const int b0 = (int)dl - (int)(16u * ((uint32_t)lane - 2u));
+                            pv = u32x4{mask_bytes(pv.x, b0), mask_bytes(pv.y, b0 - 4), mask_bytes(pv.z, b0 - 8), mask_bytes(pv.w, b0 - 12)};
+                        } else {
+                            pv = gen_chunk(P, K_PROP, me, id, 16u + dl, (uint32_t)pi, 1, (uint32_t)lane);
+                        }
+                    }
                 } else {
                     id = (uint32_t)uni((int)nx_pid_v);
                     dl = (uint32_t)uni((int)nx_dl_v);
@@ -969,16 +1023,18 @@ __global__ __launch_bounds__(64) void rlo_hop_kernel(Params P) {
 // C-ABI launch shims (rlo_world.cpp): one 64-thread workgroup per local rank, the pending table in dynamic LDS
 // (dyn_lds bytes) or, with Params.pend_hbm, in HBM (the PH instantiation); system-scope worlds run the SYS one.
 //
-// THE instantiations of rlo_hop_kernel<PH, SYS, LOC, SEND>: the launch pointer, the dynamic-LDS grant and the occupancy
-// query of each come from its row.  The one-XCD form (LOC) has no system scope, the send program (SEND) no pending
-// table and no one-XCD form.  (Rows in the order the device code has always been emitted in.)
-#define RLO_HOP_ROWS(X)                                                                          \
-    X(false, true, false, true) X(false, false, false, true) X(true, false, true, false)         \
-    X(false, false, true, false) X(true, true, false, false) X(true, false, false, false)        \
-    X(false, true, false, false) X(false, false, false, false)
+// THE instantiations of rlo_hop_kernel<PH, SYS, LOC, SEND, DECIDE>: the launch pointer, the dynamic-LDS grant and the
+// occupancy query of each come from its row.  The one-XCD form (LOC) has no system scope, the send program (SEND) no
+// pending table and no one-XCD form, the decide program (DECIDE) its pending table in LDS and no one-XCD form.  (Rows in
+// the order the device code has always been emitted in: new ones at the end.)
+#define RLO_HOP_ROWS(X)                                                                                        \
+    X(false, true, false, true, false) X(false, false, false, true, false) X(true, false, true, false, false) \
+    X(false, false, true, false, false) X(true, true, false, false, false) X(true, false, false, false, false) \
+    X(false, true, false, false, false) X(false, false, false, false, false)                                  \
+    X(false, false, false, false, true) X(false, true, false, false, true)
 
-struct HopRow { bool ph, sys, loc, send; void (*kernel)(rlo::Params); };
-#define X(PH, SYS, LOC, SEND) {PH, SYS, LOC, SEND, rlo::rlo_hop_kernel<PH, SYS, LOC, SEND>},
+struct HopRow { bool ph, sys, loc, send, decide; void (*kernel)(rlo::Params); };
+#define X(PH, SYS, LOC, SEND, DECIDE) {PH, SYS, LOC, SEND, DECIDE, rlo::rlo_hop_kernel<PH, SYS, LOC, SEND, DECIDE>},
 static const HopRow kHopRows[] = {RLO_HOP_ROWS(X)};
 #undef X
 constexpr int kHopN = (int)(sizeof kHopRows / sizeof kHopRows[0]);
@@ -994,15 +1050,18 @@ static hipError_t hop_grant(int row, size_t dyn_lds) {
 }
 
 // The row a launch runs, from (Params.mode, a pending table in HBM, Params.sys_scope): no HIP call.  The send program
-// has no pending table, whatever the world's.  -1: no such kernel (the send program, or a system-scope world, on one
-// XCD).  out (may be null): {PH, SYS, LOC, SEND}
-extern "C" int rlo_pick_hop(uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[4]) {
+// has no pending table, whatever the world's.  The decide program (MODE_DECIDE, set beside MODE_IAR | MODE_LL only) has
+// its own rows and no others: none on one XCD, none with a pending table in HBM, none with the send program.  -1: no
+// such kernel (also: the send program, or a system-scope world, on one XCD).  out (may be null): {PH, SYS, LOC, SEND, DECIDE}
+extern "C" int rlo_pick_hop(uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]) {
     const bool send = (mode & rlo::MODE_SEND) != 0, loc = (mode & rlo::MODE_XCD1) != 0;  // (RLO_PART_ONE_XCD)
+    const bool decide = (mode & rlo::MODE_DECIDE) != 0;
     const bool sys = sys_scope != 0, ph = pend_hbm && !send;
+    if (decide && (mode & (rlo::MODE_IAR | rlo::MODE_LL)) != (rlo::MODE_IAR | rlo::MODE_LL)) return -1;
     for (int i = 0; i < kHopN; i++) {
         const HopRow& r = kHopRows[i];
-        if (r.ph != ph || r.sys != sys || r.loc != loc || r.send != send) continue;
-        if (out) out[0] = r.ph, out[1] = r.sys, out[2] = r.loc, out[3] = r.send;
+        if (r.ph != ph || r.sys != sys || r.loc != loc || r.send != send || r.decide != decide) continue;
+        if (out) out[0] = r.ph, out[1] = r.sys, out[2] = r.loc, out[3] = r.send, out[4] = r.decide;
         return i;
     }
     return -1;
@@ -1015,6 +1074,8 @@ extern "C" hipError_t rlo_launch_hop(int row, const rlo::Params* p, int blocks, 
     // the send program's launch takes no dynamic LDS; the one-XCD form needs its rendezvous word
     if (r.send && (dyn_lds != 0 || !p->send_src || !p->send_dst)) return hipErrorInvalidValue;
     if (r.loc && !p->xcd_word) return hipErrorInvalidValue;
+    // the decide program's launch needs the caller's buffers (the verdict table may be absent) and a proposal place
+    if (r.decide && (!p->decide_src || !p->decide_dst || !p->decide_out || !p->decide_k || !p->decide_slot)) return hipErrorInvalidValue;
     hipError_t e = hop_grant(row, dyn_lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(r.kernel, dim3(r.loc ? 8 * blocks : blocks), dim3(64), dyn_lds, stream, *p);

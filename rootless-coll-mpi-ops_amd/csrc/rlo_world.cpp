@@ -34,7 +34,7 @@ extern "C" int rlo_pick_progress(int variant, uint32_t mode, int pend_hbm, uint3
 extern "C" hipError_t rlo_launch_progress(int row, const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream);
 extern "C" size_t rlo_kernel_static_lds(int variant);
 extern "C" hipError_t rlo_occupancy(int* blocks, size_t dyn_lds, int variant, int ll);
-extern "C" int rlo_pick_hop(uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[4]);
+extern "C" int rlo_pick_hop(uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]);
 extern "C" hipError_t rlo_launch_hop(int row, const rlo::Params* p, int blocks, size_t dyn_lds, hipStream_t stream);
 extern "C" hipError_t rlo_occupancy_hop(int row, int* blocks, size_t dyn_lds);
 
@@ -1785,6 +1785,70 @@ int rlo_program_iar(rlo_world_t* w, const rlo_iar_cfg_t* cfg, int64_t nprop, con
     return RLO_OK;
 }
 
+// the decide program: what can be refused without a GPU.  k out of range and origin == NULL are refused BEFORE an
+// element of origin / len is read (as send_check)
+int rlo_decide_check(const rlo_decide_cfg_t* cfg, int n_ranks, uint32_t max_payload) {
+    if (!cfg || n_ranks < 2 || n_ranks > 16) return RLO_E_INVAL;  // (the hop kernel's one-proposal iar worlds: plan_hop)
+    if (cfg->k < 1 || cfg->k > 0x7FFFFFFFll || !cfg->origin) return RLO_E_INVAL;
+    // 992: the slot header chunk, the PBuf header chunk and 62 data chunks = the hop kernel's 64 lanes
+    if (cfg->slot < 16u || (cfg->slot & 15u) || cfg->slot > 992u || 16ull + cfg->slot > round16(max_payload)) return RLO_E_INVAL;
+    if (!cfg->src || !cfg->dst || !cfg->decision || ((uintptr_t)cfg->src & 15u) || ((uintptr_t)cfg->dst & 15u)) return RLO_E_INVAL;
+    if (cfg->flags & ~(uint32_t)RLO_FLAG_LOG) return RLO_E_INVAL;
+    for (int64_t i = 0; i < cfg->k; i++) {
+        if (cfg->origin[i] < 0 || cfg->origin[i] >= n_ranks) return RLO_E_INVAL;
+        if (cfg->len && cfg->len[i] > cfg->slot) return RLO_E_INVAL;
+    }
+    return RLO_OK;
+}
+
+// The decide program: the iar program's rounds (pool 1, pid = the proposal's index) on the caller's device buffers.
+// Every refusal returns before base_params(w), so a refused program leaves the previous one runnable; every
+// RLO_E_INVAL condition precedes RLO_E_NOTCONNECTED (as the send programs)
+int rlo_program_decide(rlo_world_t* w, const rlo_decide_cfg_t* cfg) {
+    // RLO_PART_ONE_XCD: refused for rlo_program_send's reason (rlo_hip.h); bulk worlds and pending tables in HBM have no
+    // hop kernel for this program (rlo_pick_hop)
+    if (!w || !cfg || w->d_xcd || w->L.bulk_max || w->pend_mem) return RLO_E_INVAL;
+    const int crc = rlo_decide_check(cfg, w->L.n, w->max_payload);
+    if (crc) return crc;
+    if (!w->connected) return RLO_E_NOTCONNECTED;
+    base_params(w);
+    rlo::Params& P = w->P;
+    const int64_t k = cfg->k;
+    // per local rank its proposals, in list order: pid (the index) and data length by place
+    std::vector<uint32_t> pdl((size_t)k, 0);
+    const auto own = own_lists<int64_t>(w, k, [&](int64_t i) { return cfg->origin[i]; },
+                                        [&](size_t at, int64_t i) { pdl[at] = cfg->len ? cfg->len[i] : cfg->slot; });
+    pdl.resize(own.idx.size());
+    const std::vector<int32_t> ppid(own.idx.begin(), own.idx.end());
+    const std::vector<uint32_t> pdo(own.idx.size(), 0);  // (the kernel's prefetch loads the word; the data is at pid * slot)
+    if (w->d_prop_off.upload(own.off) || w->d_prop_pid.upload(ppid) || w->d_prop_data_off.upload(pdo) ||
+        w->d_prop_data_len.upload(pdl) || w->d_expect_dec.upload(own.expect))
+        return RLO_E_HIP;
+    // (MODE_LL: the hop kernel always rings the doorbells, and only that kernel runs this program.  The longest message:
+    // the longest proposal of the whole list, whichever part originates it, or a decision's 23-byte PBuf)
+    uint32_t max_len = 0;
+    for (int64_t i = 0; i < k; i++) max_len = std::max(max_len, cfg->len ? cfg->len[i] : cfg->slot);
+    const uint32_t max_msg = std::max(23u, 16u + max_len);
+    P.mode = rlo::MODE_IAR | rlo::MODE_LL | rlo::MODE_DECIDE;
+    P.hop_chunks = (rlo::kHdr + max_msg + 15u) / 16u;
+    P.judge_kind = rlo::JUDGE_APPROVE;  // (the judge is decide_verdict; no registry table is read)
+    P.prop_off = w->d_prop_off.p;
+    P.prop_pid = w->d_prop_pid.p;
+    P.prop_data_off = w->d_prop_data_off.p;
+    P.prop_data_len = w->d_prop_data_len.p;
+    P.expect_dec = w->d_expect_dec.p;
+    P.decide_src = static_cast<const uint8_t*>(cfg->src);
+    P.decide_verdict = cfg->verdict;
+    P.decide_dst = static_cast<uint8_t*>(cfg->dst);
+    P.decide_out = cfg->decision;
+    P.decide_k = (uint32_t)k;
+    P.decide_slot = cfg->slot;
+    const int rc = setup_log(w, cfg->flags, cfg->log_cap, false);
+    if (rc) return rc;
+    w->have_program = true;
+    return RLO_OK;
+}
+
 static void host_free(rlo_world* w) {
     if (w->cmd_host) {
         if (w->h_cmd) (void)hipHostFree(w->h_cmd);
@@ -2167,8 +2231,8 @@ struct LaunchPlan {
 // The hop kernel (rlo_hop.hip: one wave per rank, one message at a time) runs the latency and iar programs with
 // doorbells (device judges, no host service, no bulk messages) whenever every rank-wave of the part is co-resident;
 // the diagnostics modes that instrument the progress kernel's doorbell pass (phase profile, hop profile, the no-fast-path
-// A/B) keep that kernel, and so does RLO_NO_HOP (diagnostics build: A/B of the two kernels).  The send program and
-// RLO_PART_ONE_XCD worlds (every rank-wave on one XCD) run the hop kernel or nothing
+// A/B) keep that kernel, and so does RLO_NO_HOP (diagnostics build: A/B of the two kernels).  The send program, the
+// decide program and RLO_PART_ONE_XCD worlds (every rank-wave on one XCD) run the hop kernel or nothing
 static bool plan_hop(const rlo_world* w, uint32_t mode, LaunchPlan& p) {
     const rlo::Params& P = w->P;
     if (!(mode & rlo::MODE_LL) || !(mode & (rlo::MODE_LAT | rlo::MODE_IAR | rlo::MODE_SEND))) return false;
@@ -2204,7 +2268,8 @@ static LaunchPlan plan_launch(const rlo_world* w, uint32_t mode) {
     p.row = rlo_pick_progress(w->lds.variant, mode, w->P.pend_hbm != nullptr, nullptr);
     p.blocks = w->nl + (w->L.bulk_max ? (int)w->nmov : 0);
     p.dyn_lds = w->lds.dyn_lds;
-    if ((mode & rlo::MODE_SEND) || w->d_xcd || p.row < 0) p.refuse = RLO_E_INVAL;
+    // (the send and decide programs are the hop kernel's alone: never the progress kernel in its place)
+    if ((mode & (rlo::MODE_SEND | rlo::MODE_DECIDE)) || w->d_xcd || p.row < 0) p.refuse = RLO_E_INVAL;
     return p;
 }
 
@@ -2258,7 +2323,7 @@ int rlo_launch(rlo_world_t* w, void* stream) { return rlo_launch_ex(w, stream, 0
 
 int rlo_kernel_pick(int kernel, int variant, uint32_t mode, int pend_hbm, int sys_scope, uint32_t out[5]) {
     if (!out || (kernel != 0 && kernel != 1) || (kernel == 0 && variant != 8 && variant != 4 && variant != 5)) return RLO_E_INVAL;
-    out[4] = 0;
+    out[4] = 0;  // (the hop kernel's fifth argument: 1 for the decide program's rows only)
     const int row = kernel ? rlo_pick_hop(mode, pend_hbm, sys_scope, out) : rlo_pick_progress(variant, mode, pend_hbm, out);
     return row < 0 ? RLO_E_INVAL : RLO_OK;
 }

@@ -110,6 +110,12 @@ class SendStormCfg(ctypes.Structure):
                 ("rank_stride", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("log_cap", ctypes.c_uint32)]
 
 
+class DecideCfg(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int64), ("origin", ctypes.c_void_p), ("len", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("verdict", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("decision", ctypes.c_void_p),
+                ("slot", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("log_cap", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
 class HostCfg(ctypes.Structure):
     _fields_ = [("cmd_slots", ctypes.c_uint32), ("pickup_slots", ctypes.c_uint32), ("idle_timeout_s", ctypes.c_uint32),
                 ("flags", ctypes.c_uint32), ("pool", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
@@ -144,7 +150,8 @@ EXPORTS = ["rlo_topology", "rlo_children", "rlo_world_create", "rlo_world_destro
            "rlo_part_create", "rlo_part_export", "rlo_part_connect", "rlo_reset", "rlo_launch_ex",
            "rlo_stream_create", "rlo_stream_destroy",
            "rlo_program_storm", "rlo_program_latency", "rlo_program_iar", "rlo_program_send", "rlo_send_check",
-           "rlo_program_send_bulk", "rlo_send_bulk_check", "rlo_program_send_storm", "rlo_send_storm_check", "rlo_launch", "rlo_wait", "rlo_run",
+           "rlo_program_send_bulk", "rlo_send_bulk_check", "rlo_program_send_storm", "rlo_send_storm_check",
+           "rlo_program_decide", "rlo_decide_check", "rlo_launch", "rlo_wait", "rlo_run",
            "rlo_last_kernel_ms", "rlo_stats", "rlo_log", "rlo_latencies", "rlo_round_ticks", "rlo_timeline", "rlo_strerror", "rlo_last_hip_error",
            "rlo_device_error", "rlo_bulk_debug",
            "rlo_program_host", "rlo_host_post", "rlo_host_poll", "rlo_host_running", "rlo_host_cmd_count",
@@ -184,6 +191,8 @@ def load():
     L.rlo_send_bulk_check.argtypes = [ctypes.POINTER(SendBulkCfg), ctypes.c_int, ctypes.c_uint64]
     L.rlo_program_send_storm.argtypes = [vp, ctypes.POINTER(SendStormCfg)]
     L.rlo_send_storm_check.argtypes = [ctypes.POINTER(SendStormCfg), ctypes.c_int, ctypes.c_uint32]
+    L.rlo_program_decide.argtypes = [vp, ctypes.POINTER(DecideCfg)]
+    L.rlo_decide_check.argtypes = [ctypes.POINTER(DecideCfg), ctypes.c_int, ctypes.c_uint32]
     L.rlo_part_create.argtypes = [ctypes.POINTER(PartCfg), ctypes.POINTER(vp)]
     L.rlo_part_export.argtypes = [vp, vp, ctypes.c_uint32]
     L.rlo_part_connect.argtypes = [vp, vp, ctypes.c_int]

@@ -15,7 +15,11 @@ bytes as a NumPy array [rank][message][slot]; or
 {"kind": "send_bulk", "origins", "stride", "src": the source bytes (NumPy, message i at i * stride), "lens", "log",
 "fill"} (worlds with bulk messages): likewise, st["dst"] [rank][message][stride]; or
 {"kind": "send_storm", "origins", "slot", "src", "lens", "window", "log", "fill"} (run_inprocess only): the storm send
-program, buffers and st["dst"] as for "send".
+program, buffers and st["dst"] as for "send"; or
+{"kind": "decide", "origins", "slot", "src": the k * slot proposal data bytes (NumPy), "lens", "verdict": the world's
+[rank][proposal] verdict bytes (NumPy) or None, "log", "fill"} (worlds of at most 16 ranks): each part creates its own
+four device buffers (dst and the decisions pre-filled with `fill`, 0xA5); st["dst"] is the world's [rank][proposal][slot]
+places and st["decision"] its [rank][proposal] decision bytes.
 """
 import ctypes
 import multiprocessing as mp
@@ -111,6 +115,20 @@ def _program(w, spec):
         getattr(w, method)(spec["origins"], src.extent(), dst.extent(), spec[place], lens=spec.get("lens"),
                            log=spec.get("log", False), log_cap=spec.get("log_cap", 0), hist=spec.get("hist", False),
                            **{key: spec.get(key, default) for key, default in extra.items()})
+    elif spec["kind"] == "decide":
+        # the part's own device buffers, as for the send programs: the whole source, its ranks' rows of the verdict
+        # table (None: approve everything), and its ranks' places and decisions, pre-filled
+        k, slot = len(spec["origins"]), spec["slot"]
+        src = _HipBuf(w.device, np.ascontiguousarray(spec["src"], dtype=np.uint8).reshape(-1))
+        ver = None
+        if spec.get("verdict") is not None:
+            rows = np.asarray(spec["verdict"], dtype=np.uint8).reshape(-1, k)[w.rank_begin:w.rank_end]
+            ver = _HipBuf(w.device, np.ascontiguousarray(rows).reshape(-1))
+        dst = _HipBuf(w.device, w.n_local * k * slot, fill=spec.get("fill", 0xA5))
+        dec = _HipBuf(w.device, w.n_local * k, fill=spec.get("fill", 0xA5))
+        w._decide_bufs = (src, ver, dst, dec)
+        w.program_decide(spec["origins"], src.extent(), dst.extent(), dec.extent(), slot, lens=spec.get("lens"),
+                         verdict=ver.extent() if ver else None, log=spec.get("log", False), log_cap=spec.get("log_cap", 0))
     else:
         raise ValueError(spec["kind"])
 
@@ -125,6 +143,13 @@ def _collect(w, spec):
         out["dst"] = w._send_bufs[1].download().reshape(w.n_local, len(spec["origins"]), spec[_SEND[spec["kind"]][1]])
         for b in w._send_bufs:
             b.free()
+    if spec["kind"] == "decide":  # this part's places [local rank][proposal][slot] and decisions [local rank][proposal]
+        src, ver, dst, dec = w._decide_bufs
+        out["dst"] = dst.download().reshape(w.n_local, len(spec["origins"]), spec["slot"])
+        out["decision"] = dec.download().reshape(w.n_local, len(spec["origins"]))
+        for b in (src, ver, dst, dec):
+            if b is not None:
+                b.free()
     if spec.get("log"):
         cap = spec.get("log_cap", 0) or 1024
         out["logs"] = {r: w.log(r, cap=cap, payload=spec["kind"] == "storm") for r in range(w.rank_begin, w.rank_end)}
@@ -143,6 +168,8 @@ def merge(results):
         st["part_" + key] = np.concatenate([np.full(len(r["stats"]["error"]), r["info"][key]) for r in results])
     if "dst" in results[0]:  # the send program: every part's destination buffer, by world rank
         st["dst"] = np.concatenate([r["dst"] for r in results])
+    if "decision" in results[0]:  # the decide program: every part's decisions, by world rank
+        st["decision"] = np.concatenate([r["decision"] for r in results])
     logs = {}
     for r in results:
         logs.update(r.get("logs", {}))

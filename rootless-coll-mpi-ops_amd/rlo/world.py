@@ -15,6 +15,9 @@ Programs map the reference's application loops onto the device:
                 bulk world)
   send_storm() -- the same at storm rate: open-loop bcasts from any ranks in any mix on the progress kernel, small
                 and medium messages up to max_payload (program_send_storm; bcast_rows)
+  decide()   -- iar() on the caller's own device buffers: proposal data, each rank's verdict table, the data every
+                judging rank received and every rank's decisions all in device memory (program_decide, decide_rows;
+                the hop kernel only, worlds of at most 16 ranks)
 """
 import ctypes
 
@@ -221,6 +224,64 @@ class World:
                                     self.n_local)
         check(self.lib.rlo_program_send_storm(self.h, ctypes.byref(cfg)), "rlo_program_send_storm")
         self._lat_rounds = 0
+
+    def program_decide(self, origins, src, dst, decision, slot, lens=None, verdict=None, log=False, log_cap=0):
+        """rlo_program_decide (worlds of at most 16 ranks without bulk messages): proposal i (len(origins) of them, pid =
+        i) is submitted by rank origins[i] with the lens[i] (None: slot) bytes at src + i * slot, DEVICE memory, each
+        rank's proposals in list order, one in flight.  Local rank lr declines proposal i iff verdict[lr * k + i] == 0
+        (DEVICE bytes; None approves everything).  A rank that judges proposal i writes the data it received to
+        dst + (lr * k + i) * slot, and every rank the decision (0 / 1) to decision[lr * k + i], both DEVICE memory.
+        src / dst / verdict / decision: as program_send's buffers; src holds k * slot bytes, dst n_local * k * slot (both
+        16-B aligned), verdict and decision n_local * k.  slot: a multiple of 16, 16 .. 992, 16 + slot within the
+        world's max_payload.  Only the hop kernel runs this program: a launch that cannot run it raises."""
+        cfg, self._keep = _decide_cfg(origins, src, dst, decision, slot, lens, verdict, L.RLO_FLAG_LOG if log else 0,
+                                      log_cap, self.n_local)
+        check(self.lib.rlo_program_decide(self.h, ctypes.byref(cfg)), "rlo_program_decide")
+        self._lat_rounds = 0
+
+    def decide_rows(self, origins, t, verdict=None, stream=None):
+        """One consensus round per row of the contiguous CUDA tensor t of shape [k, ...]: row i (at most 992 bytes, and
+        16 bytes less than the world's max_payload) is rank origins[i]'s proposal in a one-part world of at most 16
+        ranks, all k in ONE decide launch on torch's current stream (or `stream`, a raw hipStream_t).  verdict: a uint8
+        CUDA tensor [n, k] -- rank r declines proposal i iff verdict[r, i] == 0 (its own proposals' entries are not
+        read) -- or None: everything is approved.  Returns (decided, rows): decided uint8 [n, k], 1 where rank r
+        learnt that proposal i was approved; rows of shape [n, k, ...] and t's dtype, rows[r, i] = t[i] where
+        decided[r, i] == 1 (the origin's own row included, copied in from t here) and zero elsewhere.  A row that is no
+        multiple of 16 bytes goes through a padded staging copy: t is never read past its end."""
+        import torch
+
+        if self.n_local != self.n:
+            raise ValueError("decide_rows: one-part worlds only")
+        if not (t.is_cuda and t.is_contiguous()) or t.dim() < 1:
+            raise ValueError("decide_rows: a contiguous tensor [k, ...] in device memory")
+        origin = np.asarray(origins, dtype=np.int64).reshape(-1)
+        k, n = int(t.shape[0]), self.n
+        if origin.size != k or (k and (origin.min() < 0 or origin.max() >= n)):
+            raise ValueError("decide_rows: one origin in [0, %d) per row" % n)
+        row = t[0].numel() * t.element_size() if k else 0
+        slot = decide_slot(row, self.info["slot_stride"] - 16)
+        if verdict is not None and not (verdict.is_cuda and verdict.is_contiguous() and verdict.dtype == torch.uint8 and
+                                        tuple(verdict.shape) == (n, k)):
+            raise ValueError("decide_rows: verdict is a contiguous uint8 tensor [%d, %d] in device memory" % (n, k))
+        if k == 0:
+            return torch.zeros((n, 0), dtype=torch.uint8, device=t.device), t.unsqueeze(0).repeat((n,) + (1,) * t.dim())
+        flat = t.reshape(k, -1).view(torch.uint8)
+        if slot == row and flat.data_ptr() % 16 == 0:
+            src = flat
+        else:  # a padded staging copy: t is never read past its end
+            src = torch.zeros((k, slot), dtype=torch.uint8, device=t.device)
+            src[:, :row].copy_(flat)
+        dst = torch.zeros((n, k, slot), dtype=torch.uint8, device=t.device)
+        decided = torch.zeros((n, k), dtype=torch.uint8, device=t.device)
+        self.program_decide(origin, src, dst, decided, slot, lens=None if slot == row else [row] * k, verdict=verdict)
+        if stream is None:
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+        self.launch(stream=stream)
+        self.wait()
+        out = dst[:, :, :row].contiguous()
+        out[torch.as_tensor(origin, device=t.device), torch.arange(k, device=t.device)] = flat
+        out *= decided.unsqueeze(-1)  # (a rank that judged a proposal holds its data whatever was decided)
+        return decided, out.view(t.dtype).reshape((n,) + tuple(t.shape))
 
     def bcast_rows(self, origins, t, stream=None):
         """Broadcast every row of the contiguous CUDA tensor t of shape [k, ...]: row i (at most max_payload bytes)
@@ -465,6 +526,57 @@ def _send_cfg(kind, origins, src, dst, place, lens, rank_stride, window, flags, 
         cfg.window = window
     cfg.flags, cfg.log_cap = flags, log_cap
     return cfg, [origin, ln, src, dst, cfg]
+
+
+def _decide_cfg(origins, src, dst, decision, slot, lens, verdict, flags, log_cap, n_local=None):
+    """(cfg, what it points into) of the decide program.  n_local: the local ranks of the world that is to run it -- the
+    four buffers are device buffers (_dev_extent) that must hold what the program reads and writes, src and dst 16-B
+    aligned; None: decide_check's pointers as integers.  The argument ranges themselves are the library's
+    (rlo_decide_check)"""
+    origin = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1))
+    k = int(origin.size)
+    ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.uint32).reshape(-1))
+    if ln is not None and ln.size != k:
+        raise ValueError("%s: %d lengths for %d proposals" % ("decide_check" if n_local is None else "program_decide", ln.size, k))
+    sp, dp, vp, op = src, dst, verdict, decision
+    if n_local is not None:
+        (sp, sn), (dp, dn), (op, on) = _dev_extent(src), _dev_extent(dst), _dev_extent(decision)
+        vp, vn = _dev_extent(verdict) if verdict is not None else (None, n_local * k)
+        if sp % 16 or dp % 16:
+            raise ValueError("program_decide: src and dst must be 16-byte aligned")
+        if sn < k * slot or dn < n_local * k * slot or vn < n_local * k or on < n_local * k:
+            raise ValueError("program_decide: src holds %d bytes (needs %d), dst %d (needs %d), verdict %d and decision %d "
+                             "(need %d)" % (sn, k * slot, dn, n_local * k * slot, vn, on, n_local * k))
+    cfg = L.DecideCfg()
+    cfg.k = k
+    cfg.origin = origin.ctypes.data if k else None
+    cfg.len = None if ln is None or not k else ln.ctypes.data
+    cfg.src, cfg.verdict, cfg.dst, cfg.decision = sp, vp, dp, op
+    cfg.slot, cfg.flags, cfg.log_cap = slot, flags, log_cap
+    return cfg, [origin, ln, src, dst, verdict, decision, cfg]
+
+
+def decide_check(origins, slot, n_ranks, max_payload, lens=None, src=0x1000, dst=0x1000, decision=0x1000, verdict=None,
+                 flags=0):
+    """rlo_decide_check: the argument checks of the decide program that need no GPU; returns RLO_OK or RLO_E_INVAL
+    (src / dst / decision / verdict: pointers as integers, never dereferenced)"""
+    cfg, _keep = _decide_cfg(origins, src, dst, decision, slot, lens, verdict, flags, 0)
+    return L.load().rlo_decide_check(ctypes.byref(cfg), n_ranks, max_payload)
+
+
+def decide_slot(row_bytes, max_payload):
+    """the proposal place World.decide_rows gives a row of row_bytes bytes: the row rounded up to 16 bytes, at least 16
+    (a row that is no multiple of 16 is padded in a staging copy); a row beyond 992 bytes, or beyond what a proposal
+    of the world carries (max_payload less its 16-byte frame), is refused.  Pure Python, no GPU"""
+    row_bytes, cap = int(row_bytes), -(-int(max_payload) // 16) * 16 - 16
+    if row_bytes < 0:
+        raise ValueError("decide_slot: a negative row size")
+    if row_bytes > 992:
+        raise ValueError("decide_slot: a row of %d bytes (a proposal carries at most 992)" % row_bytes)
+    slot = max(16, -(-row_bytes // 16) * 16)
+    if slot > cap:
+        raise ValueError("decide_slot: a row of %d bytes in a world of max_payload %d" % (row_bytes, max_payload))
+    return slot
 
 
 def send_fragments(nbytes, slot=1008):
