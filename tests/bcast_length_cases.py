@@ -235,16 +235,16 @@ class Expected:
             a.setflags(write=False)
 
 
-def log_arrays(w, rank, cap):
+def log_arrays(w, rank, cap, payload=True):
     """rlo_log as arrays: (records [count][8] uint32 -- kind | tag << 8, origin, from, id, len, vote, aux, payload_idx --
-    and the payload rows [cap][max_payload]); what World.log returns, without a tuple per record"""
+    and the payload rows [cap][max_payload], None without `payload`); what World.log returns, without a tuple per record"""
     from rlo import _lib as lib
 
     stride = w.info["slot_stride"] - 16
     recs = np.zeros((cap, 8), dtype=np.uint32)
-    buf = np.zeros((cap, stride), dtype=np.uint8)
-    cnt = lib.check(w.lib.rlo_log(w.h, rank, recs.ctypes.data_as(ctypes.POINTER(lib.LogRec)), cap, buf.ctypes.data, stride),
-                    "rlo_log")
+    buf = np.zeros((cap, stride), dtype=np.uint8) if payload else None
+    cnt = lib.check(w.lib.rlo_log(w.h, rank, recs.ctypes.data_as(ctypes.POINTER(lib.LogRec)), cap,
+                                  buf.ctypes.data if payload else None, stride), "rlo_log")
     return recs[:cnt], buf
 
 

@@ -83,6 +83,30 @@ class Case:
         iar_sets.check_events(logs, self.n, self.props, self.cfg, 1, stats=st, ev=self.ev)
 
 
+def launch(w, c, dst=None, dec=None, verdict=True):
+    """one launch of Case c on device buffers made here (dst and the decisions pre-filled with 0xA5): the hop kernel
+    ran; returns (stats, logs, dst bytes [n][k][slot], decision bytes [n][k])"""
+    import torch
+
+    n, k, slot = w.n_local, c.k, c.slot
+    s = torch.from_numpy(c.src.reshape(-1)).cuda()
+    v = torch.from_numpy(c.verdict.reshape(-1)).cuda() if verdict else None
+    if dst is None:
+        dst = torch.empty(n * k * slot, dtype=torch.uint8, device="cuda")
+    if dec is None:
+        dec = torch.empty(n * k, dtype=torch.uint8, device="cuda")
+    d, o = dst[:n * k * slot], dec[:n * k]
+    d.fill_(FILL)
+    o.fill_(FILL)
+    torch.cuda.synchronize()
+    w.program_decide(c.origins, s, d, o, slot, lens=c.lens, verdict=v, log=True, log_cap=4 * k + 16)
+    w.run()
+    assert w.info_now()["last_kernel"] == 1
+    st = w.stats()
+    logs = {r: w.log(r, cap=4 * k + 16) for r in range(n)}
+    return st, logs, d.cpu().numpy().reshape(n, k, slot), o.cpu().numpy().reshape(n, k)
+
+
 def start_ppm(n):
     """about 60,000 ppm at 8 ranks, scaled so a proposal's chance to pass its n - 1 judges stays about the same"""
     return 60000 * 7 // (n - 1)

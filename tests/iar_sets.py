@@ -59,8 +59,9 @@ def oracle_pool(proposals, pool):
     return pool if per and max(per.values()) > 1 else 0
 
 
-def oracle_events(n, proposals, cfg, pool):
-    ev = orc.iar(n, proposals, cfg, cap=1 << 18, pool=oracle_pool(proposals, pool))
+def oracle_events(n, proposals, cfg, pool, cap=1 << 18):
+    """cap: room for the oracle's events (a judge call, an action and a pickup per proposal and rank at the most)"""
+    ev = orc.iar(n, proposals, cfg, cap=cap, pool=oracle_pool(proposals, pool))
     assert not [e for e in ev if e[0] == orc.ORC_EV_ERROR]
     return ev
 

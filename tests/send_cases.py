@@ -98,6 +98,68 @@ def check(st, got, n, origins, lens, src):
     assert np.array_equal(st["bcast_sum"], sums)
 
 
+def launch_send(w, origins, lens, src, dst=None, **kw):
+    """one launch on device buffers made here (dst pre-filled with 0xA5): the hop kernel ran, no rank erred;
+    returns (stats, dst bytes [n_local][k][slot])"""
+    import torch
+
+    k, slot = src.shape
+    s = torch.from_numpy(src.reshape(-1)).cuda()
+    if dst is None:
+        dst = torch.empty(w.n_local * k * slot, dtype=torch.uint8, device="cuda")
+    d = dst[:w.n_local * k * slot]
+    d.fill_(FILL)
+    torch.cuda.synchronize()
+    w.program_send(origins, s, d, slot, lens=lens, **kw)
+    w.run()
+    assert w.info_now()["last_kernel"] == 1
+    st = w.stats()
+    assert (st["error"] == 0).all(), (st["error"], st["error_aux"])
+    return st, d.cpu().numpy().reshape(w.n_local, k, slot)
+
+
+def launch_send_storm(w, origins, lens, src, rank_stride=0, **kw):
+    """one launch on device buffers made here (dst pre-filled with 0xA5): the progress kernel ran, no rank erred;
+    returns (stats, dst bytes [n_local][rank_stride or k * slot])"""
+    import torch
+
+    k, slot = src.shape
+    rs = rank_stride or k * slot
+    s = torch.from_numpy(src.reshape(-1)).cuda()
+    d = torch.full((w.n_local * rs,), FILL, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    w.program_send_storm(origins, s, d, slot, lens=lens, rank_stride=rank_stride, **kw)
+    w.run()
+    assert w.info_now()["last_kernel"] == 0
+    st = w.stats()
+    assert (st["error"] == 0).all(), (st["error"], st["error_aux"])
+    return st, d.cpu().numpy().reshape(w.n_local, rs)
+
+
+def check_trees_fifo(w, n, origins, lens):
+    """every rank's log of a logged launch of the send or the storm send program (log_cap = k): one delivery record
+    per message of another rank's, without a payload copy, naming the message's origin and length; `from` is the
+    rank's parent in the origin's tree (pyoracle.tree); an origin's messages arrive in the order it sent them"""
+    import bcast_length_cases as bc
+    import pyoracle as orc
+
+    org, ln, k = np.asarray(origins, dtype=np.int64), np.asarray(lens, dtype=np.int64), len(origins)
+    parent = np.stack([orc.tree(n, o)[0] for o in range(n)]).astype(np.int64)  # [origin][rank]
+    for r in range(n):
+        recs = bc.log_arrays(w, r, k, payload=False)[0].astype(np.int64)
+        assert len(recs) == k - int((org == r).sum()), (r, len(recs))
+        kind_tag, origin, frm, ident, rlen, pidx = (recs[:, c] for c in (0, 1, 2, 3, 4, 7))
+        assert ((kind_tag & 0xffff) == (1 | TAG_BCAST << 8)).all() and (pidx == 0xFFFFFFFF).all(), r
+        assert (ident < k).all(), (r, ident.max())
+        assert (origin == org[ident]).all() and (origin != r).all() and (rlen == ln[ident]).all(), r
+        bad = np.nonzero(frm != parent[origin, r])[0]
+        assert bad.size == 0, (r, int(origin[bad[0]]), int(ident[bad[0]]), int(frm[bad[0]]))
+        by = np.argsort(origin, kind="stable")  # per-origin FIFO: an origin's records, in log order, ascend in id
+        o_s, i_s = origin[by], ident[by]
+        bad = np.nonzero((o_s[1:] == o_s[:-1]) & (i_s[1:] <= i_s[:-1]))[0]
+        assert bad.size == 0, (r, int(o_s[bad[0] + 1]), int(i_s[bad[0] + 1]))
+
+
 def forge_bus(blob):
     """the exported blob of a part, as if the part were on another GPU"""
     m = re.search(rb"[0-9a-fA-F]{4}:[0-9a-fA-F]{2}:[0-9a-fA-F]{2}\.[0-9]", blob)

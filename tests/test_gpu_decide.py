@@ -9,35 +9,12 @@ import numpy as np
 import pytest
 
 import decide_cases as dc
+from decide_cases import launch as _launch
 import iar_sets
 import pyoracle as orc
 from send_cases import FILL, forge_bus, latency_runs_clean, rlo  # noqa: F401  (rlo: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-def _launch(w, c, dst=None, dec=None, verdict=True):
-    """one launch of Case c on device buffers made here (dst and the decisions pre-filled with 0xA5): the hop kernel
-    ran; returns (stats, logs, dst bytes [n][k][slot], decision bytes [n][k])"""
-    import torch
-
-    n, k, slot = w.n_local, c.k, c.slot
-    s = torch.from_numpy(c.src.reshape(-1)).cuda()
-    v = torch.from_numpy(c.verdict.reshape(-1)).cuda() if verdict else None
-    if dst is None:
-        dst = torch.empty(n * k * slot, dtype=torch.uint8, device="cuda")
-    if dec is None:
-        dec = torch.empty(n * k, dtype=torch.uint8, device="cuda")
-    d, o = dst[:n * k * slot], dec[:n * k]
-    d.fill_(FILL)
-    o.fill_(FILL)
-    torch.cuda.synchronize()
-    w.program_decide(c.origins, s, d, o, slot, lens=c.lens, verdict=v, log=True, log_cap=4 * k + 16)
-    w.run()
-    assert w.info_now()["last_kernel"] == 1
-    st = w.stats()
-    logs = {r: w.log(r, cap=4 * k + 16) for r in range(n)}
-    return st, logs, d.cpu().numpy().reshape(n, k, slot), o.cpu().numpy().reshape(n, k)
 
 
 @pytest.mark.parametrize("n", [4, 8, 13, 16])

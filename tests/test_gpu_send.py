@@ -9,31 +9,11 @@ import functools
 import numpy as np
 import pytest
 
-import pyoracle as orc
-from send_cases import FILL, TAG_BCAST, check, forge_bus, gen, latency_runs_clean, rlo  # noqa: F401  (rlo: the fixture)
+from send_cases import FILL, check, check_trees_fifo, forge_bus, gen, latency_runs_clean, rlo  # noqa: F401  (rlo: the fixture)
+from send_cases import launch_send as _launch
 
 pytestmark = pytest.mark.gpu
 _gen = functools.partial(gen, storm=False)
-
-
-def _launch(w, origins, lens, src, dst=None, **kw):
-    """one launch on device buffers made here (dst pre-filled with 0xA5): the hop kernel ran, no rank erred;
-    returns (stats, dst bytes [n_local][k][slot])"""
-    import torch
-
-    k, slot = src.shape
-    s = torch.from_numpy(src.reshape(-1)).cuda()
-    if dst is None:
-        dst = torch.empty(w.n_local * k * slot, dtype=torch.uint8, device="cuda")
-    d = dst[:w.n_local * k * slot]
-    d.fill_(FILL)
-    torch.cuda.synchronize()
-    w.program_send(origins, s, d, slot, lens=lens, **kw)
-    w.run()
-    assert w.info_now()["last_kernel"] == 1
-    st = w.stats()
-    assert (st["error"] == 0).all(), (st["error"], st["error_aux"])
-    return st, d.cpu().numpy().reshape(w.n_local, k, slot)
 
 
 # 16 / 17 straddle the register out-ring table, 64 / 256 use the LDS table (256: its last size), 300 the computed path
@@ -58,20 +38,10 @@ def test_exact_bytes_open_loop(rlo, n, slot, k):
 def test_trees_and_per_origin_fifo(rlo, n):
     slot, k = 64, 12 * n
     origins, lens, src = _gen(n, slot, k, 2000 + n)
-    parent = {o: orc.tree(n, o)[0] for o in range(n)}
     with rlo.World(n, max_payload=slot) as w:
         st, got = _launch(w, origins, lens, src, log=True, log_cap=k)
         check(st, got, n, origins, lens, src)
-        for r in range(n):
-            rows = w.log(r, cap=k)
-            assert len(rows) == k - int((origins == r).sum())
-            last = {}
-            for kind, tag, origin, frm, ident, ln, _vote, _aux, pidx in rows:
-                assert (kind, tag) == (1, TAG_BCAST) and pidx == 0xFFFFFFFF  # a delivery record, no payload copy
-                assert origin == origins[ident] != r and ln == lens[ident]
-                assert frm == parent[origin][r], (r, origin, ident, frm)
-                assert ident > last.get(origin, -1), (r, origin, ident)  # per-origin FIFO
-                last[origin] = ident
+        check_trees_fifo(w, n, origins, lens)
 
 
 @pytest.mark.parametrize("pattern", ["rank0", "odd", "all"])

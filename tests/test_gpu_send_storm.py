@@ -13,28 +13,11 @@ import numpy as np
 import pytest
 
 import pyoracle as orc
-from send_cases import FILL, TAG_BCAST, check, forge_bus, gen, latency_runs_clean, rlo  # noqa: F401  (rlo: the fixture)
+from send_cases import FILL, check, check_trees_fifo, forge_bus, gen, latency_runs_clean, rlo  # noqa: F401  (rlo: the fixture)
+from send_cases import launch_send_storm as _launch
 
 pytestmark = pytest.mark.gpu
 _gen = functools.partial(gen, storm=True)
-
-
-def _launch(w, origins, lens, src, rank_stride=0, **kw):
-    """one launch on device buffers made here (dst pre-filled with 0xA5): the progress kernel ran, no rank erred;
-    returns (stats, dst bytes [n_local][rank_stride or k * slot])"""
-    import torch
-
-    k, slot = src.shape
-    rs = rank_stride or k * slot
-    s = torch.from_numpy(src.reshape(-1)).cuda()
-    d = torch.full((w.n_local * rs,), FILL, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    w.program_send_storm(origins, s, d, slot, lens=lens, rank_stride=rank_stride, **kw)
-    w.run()
-    assert w.info_now()["last_kernel"] == 0
-    st = w.stats()
-    assert (st["error"] == 0).all(), (st["error"], st["error_aux"])
-    return st, d.cpu().numpy().reshape(w.n_local, rs)
 
 
 # (n, max_payload, k, waves): 8 waves -- slots the small copy path stages whole, the forwarding tables (256: a CU per
@@ -83,20 +66,10 @@ def test_ring_wrap_and_refused_admissions(rlo, org):
 def test_trees_and_per_origin_fifo(rlo, n, mp):
     k = 12 * n
     origins, lens, src = _gen(n, mp, k, 2000 + n + mp)
-    parent = {o: orc.tree(n, o)[0] for o in range(n)}
     with rlo.World(n, max_payload=mp) as w:
         st, got = _launch(w, origins, lens, src, log=True, log_cap=k)
         check(st, got.reshape(n, k, mp), n, origins, lens, src)
-        for r in range(n):
-            rows = w.log(r, cap=k)
-            assert len(rows) == k - int((origins == r).sum())
-            last = {}
-            for kind, tag, origin, frm, ident, ln, _vote, _aux, pidx in rows:
-                assert (kind, tag) == (1, TAG_BCAST) and pidx == 0xFFFFFFFF  # a delivery record, no payload copy
-                assert origin == origins[ident] != r and ln == lens[ident]
-                assert frm == parent[origin][r], (r, origin, ident, frm)
-                assert ident > last.get(origin, -1), (r, origin, ident)  # per-origin FIFO
-                last[origin] = ident
+        check_trees_fifo(w, n, origins, lens)
 
 
 def test_pushed_large_payloads(rlo, monkeypatch):
